@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/s of VecEnv step() on the horizontal-locomotion task, 4096 envs per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One "step" = one lm_step over the rank's 4096 environments = reset scatter + action clamp/scale + 4 physics
@@ -11,11 +11,17 @@ resident in HBM before the timed region.  N > 1 = weak scaling: every rank owns 
 (the PPO rollout length, skrl_ppo_locomotion.py:86) the ranks all-gather a (2, 48, N_local) fp32 payload --
 the size of the rollout's returns + advantages -- over RCCL, inside the timed region.
 
-Rank 0 also reports, outside the timed region: the same workload through the drop-in boundary itself (`VecEnvRLGames.step`,
+A plain run sets up, warms up, times the K steps and prints the result line (`ms_per_step` = wall-clock milliseconds of one timed step).
+`--dump-outputs DIR` then writes what rank 0's last timed step handed back (obs, states, rew, resets, extras) as DIR/<name>.npy, float32;
+the engine seed and the action pool are fixed, so two builds run with the same arguments can be compared output for output.
+
+With `--full`, rank 0 also reports, outside the timed region: the same workload through the drop-in boundary itself (`VecEnvRLGames.step`,
 `config.vec_env_step_env_steps_per_s`: fresh output tensors and the extras dict per call, as the reference's wrapper hands them out),
 the zero-action protocol of SURVEY 8(d), the same envs with the reference's MLP policy in the loop (BASELINE config 2 names one):
 48-step rollouts as one persistent kernel (`config.mlp_policy_in_loop_...`), BASELINE config 3 and config 4's per-GPU block (`config.manipulation_...`,
-`config.cotrain_block_...`), one PD-actuator task family (`config.pd_family_...`) and BASELINE config 5 (`config.config5_...`: vertical co-training, 8192 envs, GNN in the loop).
+`config.cotrain_block_...`), one PD-actuator task family (`config.pd_family_...`) and BASELINE config 5 (`config.config5_...`: vertical co-training, 8192 envs, GNN in the loop),
+the median of 200 single launches between HIP events (`roofline.kernel_ms_single_launch_events`) and, at N = 1, the CPU oracle's rate on this
+host (`cpu_baseline`; not with --no-cpu-baseline).  A plain run leaves those fields null or out.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process starts `torch.distributed.run` with N ranks as a child BEFORE
 touching the GPU and exits with its code.
@@ -122,6 +128,8 @@ def _self_launch(args):
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
     cmd += ["--no-cpu-baseline"] if args.no_cpu_baseline else []
     cmd += ["--timed-only"] if args.timed_only else []
+    cmd += ["--full"] if args.full else []
+    cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else []
     return subprocess.call(cmd)
 
 
@@ -131,8 +139,13 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--timed-only", action="store_true", help="skip the event-timing and zero-action legs (counter collection runs: every k_step dispatch is then the timed protocol)")
+    ap.add_argument("--timed-only", action="store_true", help="with --full: skip the event-timing and other-workload legs (counter collection runs: every k_step dispatch is then the timed protocol)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the other legs (single-launch events, zero actions, VecEnvRLGames.step, "
+                                                         "policies in the loop, other workloads and sizes) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_self_launch(args))
 
@@ -201,6 +214,15 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(out_obs[0]).all() and torch.isfinite(roll_rew).all()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back, taken before any leg below steps the engine again
+        import numpy as np
+        last = args.warmup + args.steps - 1
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, x in (("obs", out_obs[last & 1]), ("states", out_states[last & 1]), ("rew", roll_rew[last % ROLLOUT]),
+                        ("resets", roll_done[last % ROLLOUT]), ("extras", out_extras)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), x.detach().cpu().numpy().astype(np.float32))
+    full_legs = args.full and not args.timed_only
 
     result = None
     if rank == 0:
@@ -208,12 +230,12 @@ def main():
         # `kernel_ms`, of which the kernel itself runs all but the ~3.5 us between dependent launches - rocprofv3's average duration of the same
         # command, profiles/r02_kernel_stats.csv, agrees to 1 %).  Events around single launches (outside the timed region) add their own
         # packets to every launch and read ~3 us more: reported as kernel_ms_single_launch_events.
-        n_ev = 0 if args.timed_only else 200
+        n_ev = 200 if full_legs else 0
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
         for i, (a, b) in enumerate(evs):
             a.record(); eng.step(pool[i % 64], None, out_obs[0], out_states[0], roll_rew[0], roll_done[0], out_extras); b.record()
         torch.cuda.synchronize(dev)
-        k_ms = sorted(a.elapsed_time(b) for a, b in evs) or [region_ms / args.steps]
+        k_ms = sorted(a.elapsed_time(b) for a, b in evs)
         step_period_ms = region_ms / args.steps                                            # launch period of the timed region, collectives included
         k_avg_ms = (region_ms - sum(a.elapsed_time(b) for a, b in ag_events)) / args.steps      # ... without the all-gather blocks: k_step's launch period
         achieved = BYTES_PER_ENV_STEP * N / (k_avg_ms * 1e-3) / 1e9
@@ -225,7 +247,7 @@ def main():
         value = world * N * args.steps / elapsed
         # second protocol of SURVEY 8(d): zero actions (standing robots, only the 300-step timeout resets); rank 0, untimed region
         zact = torch.zeros(N, 12, device=dev)
-        nz = 0 if args.timed_only else 500
+        nz = 500 if full_legs else 0
         for _ in range(nz // 10): eng.step(zact, None, out_obs[0], out_states[0], roll_rew[0], roll_done[0], out_extras)
         torch.cuda.synchronize(dev); tz = time.perf_counter()
         for _ in range(nz): eng.step(zact, None, out_obs[0], out_states[0], roll_rew[0], roll_done[0], out_extras)
@@ -233,7 +255,7 @@ def main():
         # the drop-in boundary itself: VecEnvRLGames.step (vec_env_rlgames.py:56-79) on the same workload -- fresh output tensors and the
         # extras dict per call; rank 0, untimed region
         vec_rate = None
-        if not args.timed_only:
+        if full_legs:
             import contextlib, io
             import locomanipulationrl_amd as lm
             env = lm.make_env("QuadrupedPoseControl", num_envs=N, seed=42, sim_device=str(dev), rl_device=str(dev))
@@ -249,7 +271,7 @@ def main():
         # BASELINE config 2 names an MLP policy: the same envs with the reference's 64-256-128-64 MLP (random init, seed 42) in the loop --
         # 48-step rollouts (forward on fp32 MFMA -> gaussian sampling -> step) as one persistent kernel; rank 0, untimed region
         mlp_rate = None
-        if not args.timed_only:
+        if full_legs:
             from locomanipulationrl_amd.lib import POLICY_MLP, Rollout
             from locomanipulationrl_amd.policies.mlp_model import SharedMLP, pack_mlp_params
             torch.manual_seed(42)
@@ -275,7 +297,7 @@ def main():
             e2.close()
             return r_
         extra_rates = {}
-        if not args.timed_only:
+        if full_legs:
             from locomanipulationrl_amd.engine_config import loco_cc_params, mani_params
             cq = [-1.2, 1.2, 1.2, -1.2, -1.22, -1.92, 1.92, 1.22, 1.92, 1.22, -1.22, -1.92]
             extra_rates = {
@@ -332,7 +354,7 @@ def main():
                          "peak_measured_stream": (lambda f: json.load(open(f)) if os.path.exists(f) else None)(os.path.join(ROOT, "profiles", "r04_stream_copy.json")),
                          "kernel_ms": k_avg_ms, "kernel_ms_definition": "HIP events around the timed region on the launch stream, minus the all-gather blocks, / steps = k_step's launch "
                                                                         "period (its duration + ~3.5 us between dependent launches; rocprofv3's average duration is in profiles/)",
-                         "step_period_ms": step_period_ms, "kernel_ms_single_launch_events": k_ms[len(k_ms) // 2],
+                         "step_period_ms": step_period_ms, "kernel_ms_single_launch_events": k_ms[len(k_ms) // 2] if k_ms else None,
                          "note": "1488 algorithmic B/env-step x 4096 envs per launch; the path is fp32-VALU / latency bound, see 'valu'"},
             # one wavefront per SIMD at 4096 envs: the binding resource is the wavefront's own instruction stream (fp32 VALU issue slots +
             # exposed latency), reported from the PMC passes; `step_quad_cycles` = this run's kernel time in quad-cycles at 2.4 GHz
@@ -344,7 +366,7 @@ def main():
         dist.barrier(device_ids=[dev_index]) if backend == "nccl" else dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline()
         print(json.dumps(result))
 

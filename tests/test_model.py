@@ -52,13 +52,38 @@ def test_closure_function_values():
     assert abs((d1p - d1m) / (2 * eps) - d2) < 1e-7
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference URDF (build container only)")
+def _urdf_from_golden(robot, dest):
+    """Write <dest>/<robot>.urdf from tests/golden/urdf_<robot>.npz: the reference URDF's link and joint tables (tools/extract_reference_fixtures.py)
+    with only the elements model/urdf.py reads, so that parse_urdf / compile_urdf see the same numbers as on the original file."""
+    from xml.sax.saxutils import quoteattr
+    from conftest import GOLDEN
+    t = np.load(os.path.join(GOLDEN, f"urdf_{robot}.npz"), allow_pickle=False)
+    v = lambda a: quoteattr(" ".join(repr(float(x)) for x in a))
+    out = [f"<robot name={quoteattr(str(t['robot_name']))}>"]
+    for i, name in enumerate(t["link_name"]):
+        rpy = f" rpy={v(t['link_com_rpy'][i])}" if t["link_has_com_rpy"][i] else ""
+        out.append(f"<link name={quoteattr(str(name))}><inertial><origin xyz={v(t['link_com'][i])}{rpy}/>"
+                   f"<mass value={quoteattr(repr(float(t['link_mass'][i])))}/>")
+        if t["link_has_inertia"][i]:
+            out.append("<inertia " + " ".join(f"{k}={quoteattr(repr(float(x)))}" for k, x in zip(("ixx", "ixy", "ixz", "iyy", "iyz", "izz"), t["link_inertia"][i])) + "/>")
+        out.append("</inertial></link>")
+    for i, name in enumerate(t["joint_name"]):
+        axis = f"<axis xyz={v(t['joint_axis'][i])}/>" if t["joint_has_axis"][i] else ""
+        out.append(f"<joint name={quoteattr(str(name))} type={quoteattr(str(t['joint_type'][i]))}><origin xyz={v(t['joint_xyz'][i])} rpy={v(t['joint_rpy'][i])}/>"
+                   f"<parent link={quoteattr(str(t['joint_parent'][i]))}/><child link={quoteattr(str(t['joint_child'][i]))}/>{axis}</joint>")
+    out.append("</robot>")
+    path = os.path.join(str(dest), robot + ".urdf")
+    with open(path, "w") as f:
+        f.write("\n".join(out))
+    return path
+
+
 @pytest.mark.parametrize("urdf", ["quadruped_robot_v2", "quadfinger"])
-def test_loop_closure_against_urdf(urdf):
+def test_loop_closure_against_urdf(urdf, tmp_path):
     """The analytic embedding closes the removed closed_chain_revolute joints of the URDF to < 0.05 mm
     over the whole admissible range of D = dof2 - dof3 (reset window 0.384..2.61)."""
     from locomanipulationrl_amd.model.urdf import parse_urdf, build_tree, forward_kinematics, loop_residual
-    links, joints = parse_urdf(f"/root/reference/Design/RobotURDF/robot_urdfs/{urdf}.urdf")
+    links, joints = parse_urdf(_urdf_from_golden(urdf, tmp_path))
     tree = build_tree(links, joints)
     assert len(tree.loops) == 4 and len(tree.bodies) == 21
     rng = np.random.default_rng(0)
@@ -78,10 +103,9 @@ def test_loop_closure_against_urdf(urdf):
             assert gap < 5e-5 and ang < 1e-4, (urdf, D, lp.name, gap, ang)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference URDF (build container only)")
-def test_compiled_assets_are_current(robot_model):
+def test_compiled_assets_are_current(robot_model, tmp_path):
     from locomanipulationrl_amd.model.robot_model import compile_urdf
-    m = compile_urdf("/root/reference/Design/RobotURDF/robot_urdfs/quadruped_robot_v2.urdf")
+    m = compile_urdf(_urdf_from_golden("quadruped_robot_v2", tmp_path))
     for k in ("Rt", "pt", "mass", "com", "inertia", "tip_off"):
         assert np.allclose(getattr(m, k), getattr(robot_model, k), atol=1e-12)
     assert list(m.dof) == list(robot_model.dof)
