@@ -45,8 +45,9 @@ extern "C" {
  * caller's sizeof(lm_params) and LM_TABLE_FLOATS (first three fields); lm_create returns LM_EINVAL when any of them differs from what the
  * library was built with, instead of reading a shifted struct or past the end of a shorter table.
  *   1  round 1     2  round 2 (drive_mode, 502-float table; not stamped)     3  round 3 (the stamp itself; pgs_iters per contact surface)
- *   4  round 3 (pd_second_pass replaces sat_probe: the PD-actuator families decide their clamp on the pre-step state, one pass) */
-#define LM_ABI_VERSION 4
+ *   4  round 3 (pd_second_pass replaces sat_probe: the PD-actuator families decide their clamp on the pre-step state, one pass)
+ *   5  contact-material randomisation (dr_mat, dr_mat_buckets, mat_mu_robot / mat_mu_other, friction_combine, friction_scale; LM_DR_PHYS_ROWS 43) */
+#define LM_ABI_VERSION 5
 
 /* Task / simulation constants for one task family.  Mirrors EngineParams (engine_config.py);
  * sources in the reference are cited there. */
@@ -68,7 +69,19 @@ typedef struct lm_dr_channel {
   int32_t interval;        /* frequency_interval of an on_interval entry (>= 1); 0 = on_reset entry */
   float p0[3], p1[3];      /* distribution_parameters: mean / std or low / high (one pair per component for gravity and force) */
 } lm_dr_channel;
-#define LM_DR_PHYS_ROWS 42
+/* Contact-material channels: articulation_views.<robot>.material_properties (the feet, the robot's only colliders) and
+ * rigid_prim_views.plate.material_properties.  p0 / p1 components are [static, dynamic, restitution]; only the dynamic one enters, because the
+ * contact solver has one Coulomb coefficient.  interval: >= 1 on_interval, 0 on_reset (gated by dr_min_frequency like the attributes above),
+ * LM_DR_ON_STARTUP: one draw per env, keyed by (seed, channel, env) only.  Per env and step
+ *   mu_env = max(0, friction_scale * combine(robot, other))
+ * where robot / other are mat_mu_robot / mat_mu_other after their channel's draw (other = the ground in locomotion blocks, the plate in
+ * manipulation blocks).  With both channels off the block's `mu` is used unchanged. */
+#define LM_DR_MATERIALS 2
+enum { LM_DR_MAT_ROBOT = 0, LM_DR_MAT_OTHER = 1 };
+#define LM_DR_ON_STARTUP (-1)
+enum { LM_COMBINE_AVERAGE = 0, LM_COMBINE_MIN = 1, LM_COMBINE_MULTIPLY = 2, LM_COMBINE_MAX = 3 };      /* PhysX's PxCombineMode order */
+#define LM_DR_PHYS_ROWS 43
+#define LM_DR_PHYS_MU 42   /* row of mu_env (the Coulomb coefficient the contact solve of the last step used) */
 #define LM_DR_CNT_ROWS 5   /* int64 [row][N]: observation noise counter, action noise counter, dr_step, randomization_buf, dr_reset_key */
 
 typedef struct lm_params {
@@ -111,6 +124,12 @@ typedef struct lm_params {
                                 get the implicit form of the law in ONE pass, and the 0.02 % of joint-sub-steps whose implicit torque then leaves the
                                 limit keep it.  1: those joints are put on the limit too and the sub-step is solved a second time (the applied
                                 torque never exceeds tau_max; a step then takes as long as its slowest wavefront: +6 us at 4096 envs).  DESIGN.md 3.3 */
+  /* contact-material randomisation (ABI 5; see LM_DR_MATERIALS above).  Read by the randomised kernels only, when dr_enabled */
+  lm_dr_channel dr_mat[LM_DR_MATERIALS];   /* LM_DR_MAT_ROBOT, LM_DR_MAT_OTHER; interval LM_DR_ON_STARTUP / 0 / >= 1 */
+  int32_t dr_mat_buckets[LM_DR_MATERIALS]; /* num_buckets: 0 = continuous; K >= 1: the channel's uniform variate is quantised to K levels first */
+  float mat_mu_robot, mat_mu_other;        /* nominal dynamic coefficients of the feet and of the other surface (ground / plate) */
+  int32_t friction_combine;                /* LM_COMBINE_* */
+  float friction_scale;                    /* effective / nominal coefficient (engine_config.FRICTION_SCALE) */
   /* derived by lm_create (callers leave zero) */
   float plate_si[10];      /* plate spatial inertia about its origin */
   float plate_phi[36];     /* its inverse */
@@ -140,7 +159,7 @@ typedef enum {
   LM_PTR_TERMS = 7,     /* float [LM_TERM_ROWS][N]  per-env reward terms of the last step */
   LM_PTR_DR_CNT = 8,    /* int64 [LM_DR_CNT_ROWS][N]  domain-randomisation counters */
   LM_PTR_DR_PHYS = 9    /* float [LM_DR_PHYS_ROWS][N]  attributes sampled for the last step: max efforts 12, max joint velocities 12,
-                           gravity 3, base force 3, joint damping 12 */
+                           gravity 3, base force 3, joint damping 12, mu_env 1 (row LM_DR_PHYS_MU) */
 } lm_ptr_kind;
 
 /* Create an engine for n_envs environments on the current HIP device.

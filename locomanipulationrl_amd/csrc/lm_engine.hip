@@ -155,7 +155,31 @@ LM_DEV float dr_attr(const lm_dr_channel& ch, uint32_t seed, uint32_t stream, in
   if (ch.interval == 0 && key == 0) return base;
   return dr_apply(ch.operation, base, dr_sample(seed, stream, (uint32_t)env, key, (uint32_t)idx, ch.distribution, ch.p0[comp], ch.p1[comp]));
 }
-struct DrPhys { float tmax[3], vmax[3], cj[3]; V3 g, f; };      // this lane's three joints; gravity (world); base-link force (world)
+// contact-material channel (include/lm_engine.h, LM_DR_MATERIALS): the dynamic coefficient of one surface.  on_startup entries are keyed by
+// (seed, channel, env) only; with K buckets the channel's one uniform variate is quantised to the midpoints of K equal cells before it is
+// mapped through the distribution (the inverse normal CDF for gaussian), so a channel has at most K distinct values
+#define LM_DR_STREAM_MAT 10U      // streams 10, 11 (0..8: the channels above, 9: action sampling)
+LM_DEV float dr_material(const lm_dr_channel& ch, int buckets, uint32_t seed, uint32_t stream, int env, uint32_t dr_step, uint32_t reset_key, float base) {
+  if (!ch.enabled) return base;
+  const uint32_t key = ch.interval > 0 ? dr_step / (uint32_t)ch.interval : (ch.interval < 0 ? 0U : reset_key);
+  if (ch.interval == 0 && key == 0) return base;
+  float n;
+  if (buckets > 0) {
+    float u1, u2; lm_rng_pair(lm_rng_base(seed, stream, (uint32_t)env, key), 0, &u1, &u2);
+    const float K = (float)buckets, uq = (fminf(floorf(u2 * K), K - 1.0f) + 0.5f) / K;
+    const float p0 = ch.p0[1], p1 = ch.p1[1];
+    n = ch.distribution == LM_DR_UNIFORM ? p0 + (p1 - p0) * uq
+      : ch.distribution == LM_DR_LOGUNIFORM ? expf(logf(p0) + (logf(p1) - logf(p0)) * uq)
+      : p0 + p1 * (1.41421356237309505f * erfinvf(2.0f * uq - 1.0f));
+  } else {
+    n = dr_sample(seed, stream, (uint32_t)env, key, 1U, ch.distribution, ch.p0[1], ch.p1[1]);      // component 1 = dynamic
+  }
+  return dr_apply(ch.operation, base, n);
+}
+LM_DEV float friction_combine(int mode, float a, float b) {
+  return mode == LM_COMBINE_AVERAGE ? 0.5f * (a + b) : mode == LM_COMBINE_MIN ? fminf(a, b) : mode == LM_COMBINE_MULTIPLY ? a * b : fmaxf(a, b);
+}
+struct DrPhys { float tmax[3], vmax[3], cj[3]; V3 g, f; float mu; };      // this lane's three joints; gravity (world); base-link force (world); contact mu
 LM_DEV Q4 quat_from_euler(float roll, float pitch, float yaw) {
   float sy, cy, sr, cr, sp, cp;
   sincosf(yaw * 0.5f, &sy, &cy); sincosf(roll * 0.5f, &sr, &cr); sincosf(pitch * 0.5f, &sp, &cp);
@@ -524,6 +548,7 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
   const float dt = P->dt, kd = P->kd;
   const float cjv[3] = {VAR ? (DR ? X.cj[0] : P->joint_damping) : 0.f, VAR ? (DR ? X.cj[1] : P->joint_damping) : 0.f, VAR ? (DR ? X.cj[2] : P->joint_damping) : 0.f};
   const float tmax[3] = {DR ? X.tmax[0] : P->tau_max, DR ? X.tmax[1] : P->tau_max, DR ? X.tmax[2] : P->tau_max};
+  const float mu_dr = DR ? X.mu : 0.f;      // the DrPhys X is shadowed by the contact rows inside the pass loop
   M3 Rf = quat_to_mat(F.q.w, F.q.x, F.q.y, F.q.z);
   float bn;
   {
@@ -748,9 +773,9 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
     }
     float lam[3], w[6];
     LM_STAMP(3);
-    PgsState S; pgs_setup(S, limb, P->mu, bn, vf, Wl, T, X);
+    PgsState S; pgs_setup(S, limb, DR ? mu_dr : P->mu, bn, vf, Wl, T, X);
     pgs_sweeps(S, 0, P->pgs_iters);
-    pgs_finish(S, P->mu, X, lam, w);
+    pgs_finish(S, DR ? mu_dr : P->mu, X, lam, w);
     un = sv(v3(v0f[0] + w[0], v0f[1] + w[1], v0f[2] + w[2]), v3(v0f[3] + w[3], v0f[4] + w[4], v0f[5] + w[5]));
 #pragma unroll
     for (int a = 0; a < 3; a++) qdn[a] = qdf[a] + JH[0][a] * lam[0] + JH[1][a] * lam[1] + JH[2][a] * lam[2];
@@ -1214,6 +1239,14 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
       X.cj[c] = dr_attr(P->dr[LM_DR_JOINT_DAMPING], A.seed, LM_DR_JOINT_DAMPING, env, dr_step, (uint32_t)dr_reset_key, jj[c], 0, P->joint_damping);
     }
     X.g = v3(gv[0], gv[1], gv[2]); X.f = v3(fv[0], fv[1], fv[2]);
+    // contact material: mu_env = friction_scale x combine(feet, ground / plate); the block's mu when neither channel is on
+    const lm_dr_channel& mr = P->dr_mat[LM_DR_MAT_ROBOT]; const lm_dr_channel& mo = P->dr_mat[LM_DR_MAT_OTHER];
+    X.mu = P->mu;
+    if (mr.enabled || mo.enabled) {
+      const float fr = dr_material(mr, P->dr_mat_buckets[LM_DR_MAT_ROBOT], A.seed, LM_DR_STREAM_MAT + LM_DR_MAT_ROBOT, env, dr_step, (uint32_t)dr_reset_key, P->mat_mu_robot);
+      const float fo = dr_material(mo, P->dr_mat_buckets[LM_DR_MAT_OTHER], A.seed, LM_DR_STREAM_MAT + LM_DR_MAT_OTHER, env, dr_step, (uint32_t)dr_reset_key, P->mat_mu_other);
+      X.mu = fmaxf(P->friction_scale * friction_combine(P->friction_combine, fr, fo), 0.f);
+    }
     if (active) {
       float* ph = A.dr_phys;
 #pragma unroll
@@ -1221,6 +1254,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
       if (limb == 0) {
 #pragma unroll
         for (int c = 0; c < 3; c++) { ph[(size_t)(24 + c) * N + env] = gv[c]; ph[(size_t)(27 + c) * N + env] = fv[c]; }
+        ph[(size_t)LM_DR_PHYS_MU * N + env] = X.mu;
       }
     }
   }
@@ -1881,7 +1915,7 @@ static void derive_params(lm_params* p) {
 extern "C" {
 
 const char* lm_last_error(void) { return g_err; }
-const char* lm_version(void) { return "lm_engine 0.5 (gfx950, abi 4, policy tiles on the fp16 matrix pipe)"; }
+const char* lm_version(void) { return "lm_engine 0.6 (gfx950, abi 5, policy tiles on the fp16 matrix pipe)"; }
 int lm_abi_version(void) { return LM_ABI_VERSION; }
 
 int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* params, int n_tasks, int split_env, uint32_t seed) {
@@ -1917,6 +1951,17 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
           (ch.distribution == LM_DR_LOGUNIFORM && !(ch.p0[0] > 0 && ch.p1[0] > 0)) || p.dr_min_frequency < 0)
         return fail(LM_EINVAL, "lm_create: invalid domain-randomisation channel (operation / distribution / interval / parameters)");
     }
+    for (int c = 0; c < LM_DR_MATERIALS; c++) {
+      const lm_dr_channel& ch = p.dr_mat[c];
+      if (!ch.enabled) continue;
+      if (!p.dr_enabled || ch.operation < 0 || ch.operation > 2 || ch.distribution < 0 || ch.distribution > 2 || ch.interval < LM_DR_ON_STARTUP ||
+          p.dr_mat_buckets[c] < 0 || (ch.distribution == LM_DR_LOGUNIFORM && !(ch.p0[1] > 0 && ch.p1[1] > 0)) ||
+          (c == LM_DR_MAT_OTHER && p.mode != LM_MODE_MANI))
+        return fail(LM_EINVAL, "lm_create: invalid contact-material channel (needs dr_enabled; operation / distribution / interval / num_buckets / "
+                               "parameters; the plate channel only on a manipulation block)");
+    }
+    if ((p.dr_mat[0].enabled || p.dr_mat[1].enabled) && (p.friction_combine < 0 || p.friction_combine > 3 || !(p.friction_scale >= 0.f)))
+      return fail(LM_EINVAL, "lm_create: friction_combine must be 0..3 and friction_scale >= 0 with a contact-material channel");
   }
   int device = 0;
   HIPCHK(hipGetDevice(&device));

@@ -63,12 +63,22 @@ DR_OBS_RESET, DR_OBS_INTERVAL, DR_ACT_RESET, DR_ACT_INTERVAL, DR_GRAVITY, DR_BAS
 DR_CHANNELS = 9
 DR_OPERATIONS = {"additive": 0, "scaling": 1, "direct": 2}
 DR_DISTRIBUTIONS = {"gaussian": 0, "normal": 0, "uniform": 1, "loguniform": 2, "log_uniform": 2}
+# contact-material channels (include/lm_engine.h LM_DR_MATERIALS): kept out of `dr` (the oracle's parameter block has nine slots)
+DR_MAT_ROBOT, DR_MAT_OTHER = 0, 1
+DR_ON_STARTUP = -1                  # DRChannel.interval of an on_startup material entry: one draw per env for the engine's lifetime
+FRICTION_COMBINE = {"average": 0, "min": 1, "multiply": 2, "max": 3}      # PhysX's PxCombineMode order (LM_COMBINE_*)
+
+
+def combine_friction(mode: int, a: float, b: float) -> float:
+    """The friction combine of quadruped_tasks._common (mode = FRICTION_COMBINE value)."""
+    return [0.5 * (a + b), min(a, b), a * b, max(a, b)][mode]
 
 
 @dataclass
 class DRChannel:
     """One randomised quantity: operation / distribution / distribution_parameters of the YAML; `interval` = frequency_interval
-    for on_interval entries, 0 for on_reset entries.  p0 / p1 = gaussian mean / std or uniform low / high (3 components for vectors)."""
+    for on_interval entries, 0 for on_reset entries (DR_ON_STARTUP for on_startup material entries).  p0 / p1 = gaussian mean / std or
+    uniform low / high (3 components for vectors; [static, dynamic, restitution] for the material channels)."""
     enabled: int = 0
     operation: int = 0
     distribution: int = 0
@@ -79,6 +89,10 @@ class DRChannel:
 
 def _no_dr():
     return [DRChannel() for _ in range(DR_CHANNELS)]
+
+
+def _no_mat():
+    return [DRChannel() for _ in range(2)]
 
 
 @dataclass
@@ -165,6 +179,15 @@ class EngineParams:
     dr_enabled: int = 0
     dr_min_frequency: int = 1
     dr: List[DRChannel] = field(default_factory=_no_dr)
+    # contact-material channels [robot feet, other surface]: mu_env = max(0, friction_scale x combine(robot, other)) per env,
+    # robot / other = mat_mu_robot / mat_mu_other after their channel's draw; with both channels off `mu` is used as it is.  The nominal values and
+    # friction_scale x combine(mat_mu_robot, mat_mu_other) == mu are what quadruped_tasks._common derives mu from
+    dr_mat: List[DRChannel] = field(default_factory=_no_mat)
+    dr_mat_buckets: List[int] = _f([0, 0])              # num_buckets per channel (0: continuous)
+    mat_mu_robot: float = 1.0
+    mat_mu_other: float = 1.0
+    friction_combine: int = 0                           # FRICTION_COMBINE
+    friction_scale: float = FRICTION_SCALE
     # ---- RobotOmni.take_action control mode (robot/base/robot.py:444-461), variant 0 only: 0 velocity (every task of the path), 1 position
     # (target a * act_scale rad with act_scale = pi, PD gains pd_kp / kd), 2 effort (torque a * act_scale N m with act_scale = torque limit)
     drive_mode: int = 0
@@ -201,6 +224,12 @@ class EngineParams:
     @property
     def ctrl_dt(self) -> float:
         return self.dt * self.substeps
+
+    def material_mu(self, robot: float = None, other: float = None) -> float:
+        """mu_env for the given dynamic coefficients of the feet and the other surface (nominal ones by default), as k_step_dr computes it."""
+        r = self.mat_mu_robot if robot is None else robot
+        o = self.mat_mu_other if other is None else other
+        return max(0.0, self.friction_scale * combine_friction(self.friction_combine, r, o))
 
 
 def loco_params(**kw) -> EngineParams:

@@ -17,6 +17,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 _SO = os.environ.get("LM_ENGINE_SO", os.path.join(_CSRC, "liblm_engine.so"))     # override: kernel experiments only
 
 STATE_ROWS, CNT_ROWS, NUM_OBS, NUM_STATES, NUM_ACTIONS, NUM_EXTRAS, TABLE_FLOATS, TERM_ROWS, READBACK = 115, 6, 64, 93, 12, 13, 502, 11, 99
+DR_PHYS_ROWS, DR_PHYS_MU = 43, 42       # LM_DR_PHYS_ROWS, LM_DR_PHYS_MU
 PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS = range(10)
 
 # names of the exported C symbols (checked by tests/test_abi.py against include/lm_engine.h)
@@ -36,7 +37,7 @@ class LmDrChannel(C.Structure):
                 ("p0", C.c_float * 3), ("p1", C.c_float * 3)]
 
 
-ABI_VERSION = 4          # LM_ABI_VERSION of include/lm_engine.h this mirror was written against
+ABI_VERSION = 5          # LM_ABI_VERSION of include/lm_engine.h this mirror was written against
 
 
 class LmParams(C.Structure):
@@ -65,6 +66,8 @@ class LmParams(C.Structure):
         ("torque_div", C.c_float), ("power_scale", C.c_float), ("target_err_scale", C.c_float), ("rot_dec_scale", C.c_float),
         ("rot_dec_thresh", C.c_float), ("cc_update_last_tgt", C.c_int32), ("acc_substeps", C.c_int32),
         ("dr_enabled", C.c_int32), ("dr_min_frequency", C.c_int32), ("dr", LmDrChannel * 9), ("drive_mode", C.c_int32), ("pd_second_pass", C.c_int32),
+        ("dr_mat", LmDrChannel * 2), ("dr_mat_buckets", C.c_int32 * 2), ("mat_mu_robot", C.c_float), ("mat_mu_other", C.c_float),
+        ("friction_combine", C.c_int32), ("friction_scale", C.c_float),
         ("plate_si", C.c_float * 10), ("plate_phi", C.c_float * 36), ("ctrl_dt_inv", C.c_float), ("acc_dt_inv", C.c_float),
     ]
 
@@ -78,6 +81,9 @@ def make_params(ep, clip_obs: float = 5.0, clip_actions: float = 1.0) -> LmParam
         raise ValueError("EngineParams.solver != 0 is an oracle-only experiment (DESIGN.md 2.2): the engine implements solver 0")
     if getattr(ep, "pyramid", 0):
         raise ValueError("EngineParams.pyramid is an oracle-only evidence switch: the engine implements the friction cone only")
+    if any(ch.enabled for ch in ep.dr_mat) and abs(ep.material_mu() - ep.mu) > 1e-6 * max(1.0, abs(ep.mu)):
+        raise ValueError(f"EngineParams: mu {ep.mu} differs from friction_scale x combine(mat_mu_robot, mat_mu_other) = {ep.material_mu()}: a "
+                         "contact-material channel would move the nominal coefficient (set the material fields consistently with mu)")
     p = LmParams()
     p.abi_version, p.params_size, p.table_floats = ABI_VERSION, C.sizeof(LmParams), TABLE_FLOATS      # the stamp lm_create checks
     for name, _ in LmParams._fields_:
@@ -87,11 +93,16 @@ def make_params(ep, clip_obs: float = 5.0, clip_actions: float = 1.0) -> LmParam
             p.clip_obs = float(clip_obs); continue
         if name == "clip_actions":
             p.clip_actions = float(clip_actions); continue
-        if name == "dr":
-            for i, ch in enumerate(ep.dr):
-                p.dr[i].enabled, p.dr[i].operation, p.dr[i].distribution, p.dr[i].interval = int(ch.enabled), int(ch.operation), int(ch.distribution), int(ch.interval)
+        if name in ("dr", "dr_mat"):
+            dst = getattr(p, name)
+            for i, ch in enumerate(getattr(ep, name)):
+                dst[i].enabled, dst[i].operation, dst[i].distribution, dst[i].interval = int(ch.enabled), int(ch.operation), int(ch.distribution), int(ch.interval)
                 for c in range(3):
-                    p.dr[i].p0[c] = float(ch.p0[c]); p.dr[i].p1[c] = float(ch.p1[c])
+                    dst[i].p0[c] = float(ch.p0[c]); dst[i].p1[c] = float(ch.p1[c])
+            continue
+        if name == "dr_mat_buckets":
+            for i, k in enumerate(ep.dr_mat_buckets):
+                p.dr_mat_buckets[i] = int(k)
             continue
         val = getattr(ep, name)
         if isinstance(val, (list, tuple, np.ndarray)):
@@ -228,7 +239,8 @@ class Engine:
         self.stats_i64 = self._wrap(PTR_STATS, (6,), "<i8")
         self._stats_i32 = self._wrap(PTR_STATS, (16,), "<i4")         # word 15: contained blow-ups
         self.dr_cnt = self._wrap(PTR_DR_CNT, (5, N), "<i8")          # domain-randomisation counters
-        self.dr_phys = self._wrap(PTR_DR_PHYS, (42, N), "<f4")       # attributes sampled for the last step
+        self.dr_phys = self._wrap(PTR_DR_PHYS, (42, N), "<f4")       # attributes sampled for the last step (rows 0..41)
+        self.dr_mu = self._wrap(PTR_DR_PHYS, (DR_PHYS_ROWS, N), "<f4")[DR_PHYS_MU]      # row 42: the contact mu of each env in the last step
 
     def _view(self, kind, shape):
         if kind not in self._views:

@@ -17,7 +17,7 @@ from __future__ import annotations
 import sys
 from typing import List, Optional
 
-from ..engine_config import FRICTION_SCALE, MODE_LOCO, MODE_MANI, EngineParams
+from ..engine_config import FRICTION_COMBINE, FRICTION_SCALE, MODE_LOCO, MODE_MANI, EngineParams
 from ..robot.quadruped_robot import (QuadrupedRobotOVFixedBaseOmni, QuadrupedRobotOVOmni, QuadrupedRobotVerticalOVFixedOmni,
                                      QuadrupedRobotVerticalOVOmni)
 from .base.rl_task import CC_EXTRAS_KEYS, RLTask
@@ -90,6 +90,13 @@ class _QuadrupedTask(RLTask):
             print(f"[locomanipulationrl_amd] foot friction: nominal (YAML, combined) {mu:.3g} x sim.engine.friction_scale {scale:.3g} = {mu * scale:.3g} "
                   f"(fitted on the reference's PhysX recordings, parity unpinned; set sim.engine.friction_scale: 1.0 for the YAML value)", file=sys.stderr)
         mu *= scale
+        # nominal materials of the contact-material channels: friction_scale x combine(feet, other) reproduces mu above.  `other` is
+        # the ground material where it is combined; elsewhere (the plate, a ground without a material) it carries the scene's default material, so
+        # the combine gives mu_body back (1.0 under multiply for the same reason)
+        comb = eng.get("friction_combine", "average")
+        combined = gnd is not None and kw.get("mode", MODE_LOCO) == MODE_LOCO
+        mat_fields = dict(mat_mu_robot=mu_body, mat_mu_other=mu_g if combined else (1.0 if comb == "multiply" else mu_body),
+                          friction_combine=FRICTION_COMBINE.get(comb, -1), friction_scale=scale)
         rd = robot.robot_description
         if rd.control_mode not in ("velocity", "position", "effort"):          # robot.py:323-333
             raise AttributeError(f"Invalid control mode name {rd.control_mode!r}")
@@ -146,7 +153,10 @@ class _QuadrupedTask(RLTask):
                         power_scale=float(self.mechanical_power_penalty_scale), target_err_scale=float(self.position_target_error_penalty_scale),
                         rot_dec_scale=float(self.rot_dist_decreasing_reward_scale), rot_dec_thresh=float(self.no_rot_dist_decreasing_reward_thresh),
                         cc_update_last_tgt=int(self.update_last_targets))
-        base.update(self._dr_randomizer.engine_dr())
+        base.update(mat_fields)
+        base.update(self._dr_randomizer.engine_dr(kw.get("mode", MODE_LOCO)))
+        if any(ch.enabled for ch in base.get("dr_mat", [])) and base["friction_combine"] < 0:
+            raise ValueError(f"sim.engine.friction_combine {comb!r}: one of {sorted(FRICTION_COMBINE)} is needed with material_properties randomisation")
         base.update(kw)
         return EngineParams(**base)
 

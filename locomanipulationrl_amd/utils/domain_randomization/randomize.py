@@ -20,7 +20,11 @@ Supported entries (everything the reference's YAMLs enable):
     articulation_views.<robot>.joint_friction          accepted and ignored with a warning (joint friction itself is not modelled)
     articulation_views.<robot>.scale on_startup        accepted with a warning: factors drawn and recorded, not applied (see
                                                        apply_on_startup_domain_randomization: the reference's call does not rescale the links either)
-Anything else (mass, density, material_properties, stiffness ...) raises NotImplementedError when
+    articulation_views.<robot>.material_properties     on_startup | on_reset | on_interval, [static, dynamic, restitution] parameters,
+    rigid_prim_views.plate.material_properties         optional num_buckets: the contact friction of the feet / of the plate per env
+                                                       (EngineParams.dr_mat).  Only the dynamic component enters; a
+                                                       static or restitution component that would change warns (not modelled)
+Anything else (mass, density, material_properties of other views, stiffness ...) raises NotImplementedError when
 `randomize: True` - a silently ignored randomisation would be worse than a loud one."""
 from __future__ import annotations
 
@@ -28,8 +32,9 @@ from typing import List
 
 import numpy as np
 
-from ...engine_config import (DR_ACT_INTERVAL, DR_ACT_RESET, DR_BASE_FORCE, DR_CHANNELS, DR_DISTRIBUTIONS, DR_GRAVITY, DR_JOINT_DAMPING, DR_MAX_EFFORT,
-                              DR_MAX_VELOCITY, DR_OBS_INTERVAL, DR_OBS_RESET, DR_OPERATIONS, DRChannel)
+from ...engine_config import (DR_ACT_INTERVAL, DR_ACT_RESET, DR_BASE_FORCE, DR_CHANNELS, DR_DISTRIBUTIONS, DR_GRAVITY, DR_JOINT_DAMPING, DR_MAT_OTHER,
+                              DR_MAT_ROBOT, DR_MAX_EFFORT, DR_MAX_VELOCITY, DR_OBS_INTERVAL, DR_OBS_RESET, DR_ON_STARTUP, DR_OPERATIONS, MODE_MANI,
+                              DRChannel)
 
 _ON_RESET_KEYS = ("operation", "distribution", "distribution_parameters")
 _ON_INTERVAL_KEYS = ("frequency_interval", "operation", "distribution", "distribution_parameters")
@@ -57,6 +62,62 @@ def _channel(where: str, entry: dict, trigger: str, vector: bool) -> DRChannel:
     return DRChannel(enabled=1, operation=DR_OPERATIONS[op], distribution=DR_DISTRIBUTIONS[dist], interval=interval, p0=p0, p1=p1)
 
 
+_MAT_COMPONENTS = ("static", "dynamic", "restitution")
+PLATE_VIEW = "plate"          # the plate's RigidPrimView name (reference objects/plate.py:8, objects/base/rigid_object.py:30)
+
+
+def _degenerate(dist: int, p0: float, p1: float):
+    """The one value a distribution can take, or None (gaussian: std 0; uniform / loguniform: low == high)."""
+    if dist == DR_DISTRIBUTIONS["gaussian"]:
+        return p0 if p1 == 0 else None
+    return p0 if p0 == p1 else None
+
+
+def _changes(op: int, dist: int, p0: float, p1: float, nominal: float) -> bool:
+    """Whether a channel component would move a quantity from its nominal value."""
+    v = _degenerate(dist, p0, p1)
+    if op == DR_OPERATIONS["additive"]:
+        return v != 0.0
+    if op == DR_OPERATIONS["scaling"]:
+        return nominal != 0.0 and v != 1.0
+    return v != nominal
+
+
+def _material_channel(where: str, entry: dict, trigger: str):
+    """One material_properties trigger -> (DRChannel over [static, dynamic, restitution], num_buckets)."""
+    need = _ON_INTERVAL_KEYS if trigger == "on_interval" else _ON_RESET_KEYS
+    if entry is None or not set(need).issubset(entry.keys()):          # randomize.py:357-359,376-378
+        raise ValueError(f"Please ensure the following randomization parameters for {where} {trigger} are provided: " + ", ".join(need) + ".")
+    op, dist = str(entry["operation"]), str(entry["distribution"])
+    if op not in DR_OPERATIONS or dist not in DR_DISTRIBUTIONS:
+        raise ValueError(f"{where} {trigger}: unsupported operation {op!r} or distribution {dist!r}")
+    raw = entry["distribution_parameters"]
+    try:
+        prm = np.asarray(raw, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{where} {trigger}: distribution_parameters must be numbers, got {raw!r}") from None
+    if prm.shape == (2,):          # one pair for all three components (randomize.py:445-447)
+        prm = np.repeat(prm[:, None], 3, axis=1)
+    if prm.shape != (2, 3) or not np.isfinite(prm).all():
+        raise ValueError(f"{where} {trigger}: distribution_parameters must be [[static, dynamic, restitution], [static, dynamic, restitution]] "
+                         f"(or [a, b] for all three), got {raw!r}" + (" - operation 'direct' needs the values it sets" if op == "direct" else ""))
+    if dist in ("loguniform", "log_uniform") and not (prm > 0).all():
+        raise ValueError(f"{where} {trigger}: loguniform parameters must be positive")
+    buckets = 0
+    if "num_buckets" in entry:          # randomize.py:361-362: optional
+        b = entry["num_buckets"]
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or b < 1:
+            raise ValueError(f"{where} {trigger}: num_buckets must be a positive integer, got {b!r}")
+        buckets = int(b)
+    interval = {"on_startup": DR_ON_STARTUP, "on_reset": 0}.get(trigger)
+    if interval is None:
+        interval = int(entry["frequency_interval"])
+        if interval < 1:
+            raise ValueError(f"{where}: frequency_interval must be >= 1")
+    ch = DRChannel(enabled=1, operation=DR_OPERATIONS[op], distribution=DR_DISTRIBUTIONS[dist], interval=interval, p0=prm[0].tolist(), p1=prm[1].tolist())
+    return ch, buckets
+
+
 class Randomizer:
     def __init__(self, sim_config):
         self._cfg = sim_config.task_config
@@ -65,6 +126,8 @@ class Randomizer:
         self.min_frequency = 1
         self.active_domain_randomizations = dict()
         self._channels: List[DRChannel] = [DRChannel() for _ in range(DR_CHANNELS)]
+        self._mat_channels: List[DRChannel] = [DRChannel(), DRChannel()]          # [robot feet, plate] (EngineParams.dr_mat)
+        self._mat_buckets: List[int] = [0, 0]
         self._observations_dr_params = None
         self._actions_dr_params = None
         self.startup_scales = dict()          # (group, view) -> per-env factors drawn by apply_on_startup_domain_randomization
@@ -101,8 +164,8 @@ class Randomizer:
         for group in ("rigid_prim_views", "articulation_views"):
             for view, attrs in (params.get(group) or {}).items():
                 for attribute, entry in (attrs or {}).items():
-                    if entry is None or "on_startup" not in entry:
-                        continue
+                    if entry is None or "on_startup" not in entry or attribute == "material_properties":
+                        continue          # material_properties on_startup is a channel of the engine (set_up_domain_randomization)
                     st = entry["on_startup"]
                     if not set(_ON_RESET_KEYS).issubset(st.keys()):          # randomize.py:75-77,104-106
                         raise ValueError(f"Please ensure the following randomization parameters for {view} {attribute} on_startup are provided: "
@@ -157,6 +220,9 @@ class Randomizer:
                     for attribute, entry in (attrs or {}).items():
                         if attribute in ("scale", "mass", "density"):
                             continue          # on_startup entries, handled (refused) above
+                        if attribute == "material_properties" and view == PLATE_VIEW:
+                            self._set_up_material(("rigid_prim_views", view, attribute), entry, DR_MAT_OTHER)
+                            continue
                         if attribute != "force":
                             raise NotImplementedError(f"domain randomisation of rigid_prim_views.{view}.{attribute} is not implemented")
                         self._set_up_attribute(("rigid_prim_views", view, attribute), entry, DR_BASE_FORCE, vector=True)
@@ -164,6 +230,9 @@ class Randomizer:
                 for view, attrs in (body or {}).items():
                     for attribute, entry in (attrs or {}).items():
                         if attribute == "scale":
+                            continue
+                        if attribute == "material_properties":          # the feet: the robot's only colliders
+                            self._set_up_material(("articulation_views", view, attribute), entry, DR_MAT_ROBOT)
                             continue
                         if attribute == "joint_friction":          # the joint friction coefficient itself is not modelled: scaling it changes nothing
                             import warnings
@@ -199,12 +268,36 @@ class Randomizer:
                 self._channels[ch] = _channel(".".join(key), entry[trigger], trigger, vector)
                 self.active_domain_randomizations[key + (trigger,)] = np.array(entry[trigger]["distribution_parameters"])
 
+    def _set_up_material(self, key, entry, ch):
+        """material_properties of the robot (ch = DR_MAT_ROBOT) or the plate (DR_MAT_OTHER): one trigger, dynamic component into the engine."""
+        where = ".".join(key)
+        if entry is None:
+            raise ValueError(f"Randomization parameters for {where} is not provided.")
+        triggers = [t for t in ("on_startup", "on_reset", "on_interval") if t in entry]
+        if len(triggers) != 1:
+            raise NotImplementedError(f"{where}: give exactly one of on_startup, on_reset, on_interval")
+        trigger = triggers[0]
+        self._mat_channels[ch], self._mat_buckets[ch] = _material_channel(where, entry[trigger], trigger)
+        self.active_domain_randomizations[key + (trigger,)] = np.array(entry[trigger]["distribution_parameters"])
+        c = self._mat_channels[ch]
+        mat = (self._cfg.get("sim", {}) or {}).get("default_physics_material", {}) or {}          # the feet and the plate carry the scene's default material
+        nominal = (float(mat.get("static_friction", 1.0)), None, float(mat.get("restitution", 0.0)))
+        unmodelled = [name for i, name in enumerate(_MAT_COMPONENTS) if i != 1 and _changes(c.operation, c.distribution, c.p0[i], c.p1[i], nominal[i])]
+        if unmodelled:
+            import warnings
+            warnings.warn(f"{where} {trigger}: the {' and '.join(unmodelled)} component(s) are drawn for the record but not modelled by this engine "
+                          "(one Coulomb coefficient, the dynamic one; no restitution); only dynamic_friction is randomised")
+
     # ------------------------------------------------------------------ engine side
-    def engine_dr(self) -> dict:
-        """Fields of EngineParams describing the randomisation (all channels off when randomize is False)."""
+    def engine_dr(self, mode: int = None) -> dict:
+        """Fields of EngineParams describing the randomisation (all channels off when randomize is False).  `mode`: the block's task mode - the
+        plate's material channel belongs to manipulation blocks only."""
         if not self.randomize:
             return dict(dr_enabled=0, dr_min_frequency=1, dr=[DRChannel() for _ in range(DR_CHANNELS)])
-        return dict(dr_enabled=1, dr_min_frequency=int(self.min_frequency), dr=list(self._channels))
+        mat = list(self._mat_channels); buckets = list(self._mat_buckets)
+        if mode != MODE_MANI:
+            mat[DR_MAT_OTHER] = DRChannel(); buckets[DR_MAT_OTHER] = 0
+        return dict(dr_enabled=1, dr_min_frequency=int(self.min_frequency), dr=list(self._channels), dr_mat=mat, dr_mat_buckets=buckets)
 
     # The wrapper calls these two exactly where the reference does (vec_env_rlgames.py:56-58,70-72).  The noise has already been /
     # will be applied inside lm_step with the reference's counter semantics (randomize.py:212-306), so they hand the tensor through.
