@@ -83,6 +83,20 @@ enum { LM_COMBINE_AVERAGE = 0, LM_COMBINE_MIN = 1, LM_COMBINE_MULTIPLY = 2, LM_C
 #define LM_DR_PHYS_ROWS 43
 #define LM_DR_PHYS_MU 42   /* row of mu_env (the Coulomb coefficient the contact solve of the last step used) */
 #define LM_DR_CNT_ROWS 5   /* int64 [row][N]: observation noise counter, action noise counter, dr_step, randomization_buf, dr_reset_key */
+/* Reset-state channels: the state an env is reset to, drawn inside lm_step at the moment of the reset.  They live in a struct of
+ * their own, handed over with lm_set_reset_randomization, so that lm_params keeps its layout.  on_reset only (interval 0).  A reset that passes
+ * the dr_min_frequency gate draws, keyed by (seed, stream, env, new episode number, component); one that does not resets to the nominal state.
+ *   LM_DR_RESET_JOINT_POS     12 components (one draw per driven joint, scalar parameters p0[0] / p1[0]) on init_q
+ *   LM_DR_RESET_JOINT_VEL     12 components, scalar parameters, on the nominal 0: additive or direct
+ *   LM_DR_RESET_POSITION      3 components, per-component parameters, on the free body's nominal position
+ *   LM_DR_RESET_ORIENTATION   3 Euler angles (roll, pitch, yaw), per-component parameters, turned into a quaternion q_draw:
+ *                             direct: q = q_draw; additive: q = q_draw (x) q_nominal (applied in the world frame after the nominal one)
+ * The free body is the base in locomotion blocks and the plate in manipulation blocks.  No clamping to the joint ranges: a draw outside
+ * d1_rst / d23_rst makes the env reset again on the next step.  The random streams are 12..15 (after the material streams 10, 11). */
+#define LM_DR_RESET_CHANNELS 4
+enum { LM_DR_RESET_JOINT_POS = 0, LM_DR_RESET_JOINT_VEL = 1, LM_DR_RESET_POSITION = 2, LM_DR_RESET_ORIENTATION = 3 };
+typedef struct lm_reset_dr { lm_dr_channel ch[LM_DR_RESET_CHANNELS]; } lm_reset_dr;
+#define LM_DR_RESET_ROWS 31  /* float [row][N]: q 12, qd 12, free-body position 3, free-body quaternion (w, x, y, z) 4 */
 
 typedef struct lm_params {
   int32_t abi_version;     /* LM_ABI_VERSION of the header the caller was compiled against */
@@ -158,8 +172,10 @@ typedef enum {
                            uint32 at byte 60: envs whose state became non-finite / exploded and was replaced by the reset pose */
   LM_PTR_TERMS = 7,     /* float [LM_TERM_ROWS][N]  per-env reward terms of the last step */
   LM_PTR_DR_CNT = 8,    /* int64 [LM_DR_CNT_ROWS][N]  domain-randomisation counters */
-  LM_PTR_DR_PHYS = 9    /* float [LM_DR_PHYS_ROWS][N]  attributes sampled for the last step: max efforts 12, max joint velocities 12,
+  LM_PTR_DR_PHYS = 9,   /* float [LM_DR_PHYS_ROWS][N]  attributes sampled for the last step: max efforts 12, max joint velocities 12,
                            gravity 3, base force 3, joint damping 12, mu_env 1 (row LM_DR_PHYS_MU) */
+  LM_PTR_DR_RESET_STATE = 10 /* float [LM_DR_RESET_ROWS][N]  the state each env was last reset to by lm_step (nominal resets included);
+                           randomised engines only (NULL otherwise) */
 } lm_ptr_kind;
 
 /* Create an engine for n_envs environments on the current HIP device.
@@ -175,6 +191,14 @@ typedef enum {
 int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* params, int n_tasks,
               int split_env, uint32_t seed);
 int lm_destroy(lm_engine* h);
+
+/* Reset-state randomisation of parameter block `block` (0, or 1 on a two-task engine): validates *rd and copies it to device memory owned
+ * by the handle; later lm_step launches draw from it (see LM_DR_RESET_CHANNELS above).  All four channels are off after lm_create.
+ * LM_EINVAL: engine without dr_enabled; block out of range; an enabled channel with a bad operation / distribution, an interval other
+ * than 0 (on_reset is the only trigger), `scaling` on the joint velocities (nominal 0) or on the orientation (a quaternion is not scaled),
+ * log-uniform with non-positive bounds, or non-finite parameters.  Synchronous (a blocking copy): call it before the first step and not
+ * while a graph that contains lm_step is being captured. */
+int lm_set_reset_randomization(lm_engine* h, int block, const lm_reset_dr* rd);
 
 /* One VecEnvRLGames.step(): reset flagged envs, clamp + apply actions, controlFrequencyInv physics
  * sub-steps, observations / reward / termination.  (vec_env_rlgames.py:56-79)

@@ -102,6 +102,7 @@ struct lm_engine {
   lm_params* d_params;     // [2]
   float* d_table;
   float* d_state; int64_t* d_cnt; int64_t* d_drc; float* d_dr_phys; int dr_enabled;
+  lm_reset_dr* d_reset_dr; // randomised engines: the reset-state channels of the two blocks, followed by float [LM_DR_RESET_ROWS][N] (LM_PTR_DR_RESET_STATE)
   float *d_obs, *d_states, *d_rew, *d_extras, *d_terms; long long* d_acc; int acc_rows;
   bool view_obs, view_states, view_terms;      // lm_ptr() handed out obs_buf / states_buf / the reward terms: lm_step keeps them current from then on
   char* d_stats;           // int64 {num_successes, num_resets} x {all, first task, second task}; float success_rate x 3 at byte 48;
@@ -159,6 +160,7 @@ LM_DEV float dr_attr(const lm_dr_channel& ch, uint32_t seed, uint32_t stream, in
 // (seed, channel, env) only; with K buckets the channel's one uniform variate is quantised to the midpoints of K equal cells before it is
 // mapped through the distribution (the inverse normal CDF for gaussian), so a channel has at most K distinct values
 #define LM_DR_STREAM_MAT 10U      // streams 10, 11 (0..8: the channels above, 9: action sampling)
+#define LM_DR_STREAM_RESET 12U    // streams 12..15: the reset-state channels (LM_DR_RESET_*)
 LM_DEV float dr_material(const lm_dr_channel& ch, int buckets, uint32_t seed, uint32_t stream, int env, uint32_t dr_step, uint32_t reset_key, float base) {
   if (!ch.enabled) return base;
   const uint32_t key = ch.interval > 0 ? dr_step / (uint32_t)ch.interval : (ch.interval < 0 ? 0U : reset_key);
@@ -1184,6 +1186,8 @@ struct StepArgs {
   float* dr_phys;   // [LM_DR_PHYS_ROWS][N] attributes sampled for this step (k_step_dr only)
   int kind[2];      // variant * 2 + (mode == LM_MODE_MANI) of the two parameter blocks: the kernels pick their specialisation from the kernel
                     // arguments, so the first loads of the step do not wait for a round trip to the parameter block
+  const lm_reset_dr* reset_dr;      // reset-state channels of the two blocks, followed by float [LM_DR_RESET_ROWS][N]: the state each env was last
+                                    // reset to (k_step_dr / k_step_dr_pd only; kept last so that no other member moves)
 };
 
 template <int MODE, int VAR, int DR, int DEFER = 0>
@@ -1209,7 +1213,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
     q[a] = st[(size_t)(R_Q + jj[a]) * N + env]; qd[a] = st[(size_t)(R_QD + jj[a]) * N + env];
     act[a] = A.actions[(size_t)env * 12 + jj[a]];
   }
-  DrPhys X; uint32_t dr_step = 0; int64_t dr_rand_buf = 0, dr_reset_key = 0;
+  DrPhys X; uint32_t dr_step = 0; int64_t dr_rand_buf = 0, dr_reset_key = 0; bool reset_draw = false;
   if (DR) {
     // ---- action noise on the raw actions (vec_env_rlgames.py:56-58; randomize.py:237-259): correlated noise keyed by the episode this
     // step belongs to (redrawn exactly when the reset flag is set), uncorrelated noise every frequency_interval calls
@@ -1228,7 +1232,8 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
     }
     if (active && limb == 0) dc[1 * (size_t)N + env] = ac;
     // ---- gated on_reset randomisation (quadruped_pose_control.py:224-228), then this control step's physics attributes
-    if (do_reset && dr_rand_buf >= P->dr_min_frequency) { dr_reset_key = ep_now; dr_rand_buf = 0; }
+    reset_draw = do_reset && dr_rand_buf >= P->dr_min_frequency;
+    if (reset_draw) { dr_reset_key = ep_now; dr_rand_buf = 0; }
     const float g0[3] = {0.f, 0.f, -P->gravity}; float gv[3], fv[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -1267,6 +1272,45 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
     const float* ip = (MODE == 0) ? P->init_base_pos : P->init_plate_pos; const float* iq = (MODE == 0) ? P->init_base_quat : P->init_plate_quat;
     F.p = v3(ip[0], ip[1], ip[2]); F.q.w = iq[0]; F.q.x = iq[1]; F.q.y = iq[2]; F.q.z = iq[3];
     lin = v3(0, 0, 0); ang = v3(0, 0, 0);
+    if (DR) {
+      // ---- reset-state channels: a reset that passed the min_frequency gate draws the state it starts from, keyed by the new
+      // episode number; the draws and the record stay inside this branch, which a wavefront without a resetting lane skips
+      const lm_reset_dr* RD = A.reset_dr + ((env0 >= A.split) ? 1 : 0);
+      if (reset_draw) {
+        const uint32_t key = (uint32_t)dr_reset_key, e = (uint32_t)env;
+        const lm_dr_channel& cq = RD->ch[LM_DR_RESET_JOINT_POS]; const lm_dr_channel& cv = RD->ch[LM_DR_RESET_JOINT_VEL];
+        const lm_dr_channel& cp = RD->ch[LM_DR_RESET_POSITION]; const lm_dr_channel& co = RD->ch[LM_DR_RESET_ORIENTATION];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+          if (cq.enabled) q[a] = dr_apply(cq.operation, q[a], dr_sample(A.seed, LM_DR_STREAM_RESET + LM_DR_RESET_JOINT_POS, e, key, (uint32_t)jj[a], cq.distribution, cq.p0[0], cq.p1[0]));
+          if (cv.enabled) qd[a] = dr_apply(cv.operation, 0.f, dr_sample(A.seed, LM_DR_STREAM_RESET + LM_DR_RESET_JOINT_VEL, e, key, (uint32_t)jj[a], cv.distribution, cv.p0[0], cv.p1[0]));
+        }
+        if (cp.enabled) {
+          float pc[3];
+#pragma unroll
+          for (int c = 0; c < 3; c++) pc[c] = dr_apply(cp.operation, ip[c], dr_sample(A.seed, LM_DR_STREAM_RESET + LM_DR_RESET_POSITION, e, key, (uint32_t)c, cp.distribution, cp.p0[c], cp.p1[c]));
+          F.p = v3(pc[0], pc[1], pc[2]);
+        }
+        if (co.enabled) {
+          float eu[3];
+#pragma unroll
+          for (int c = 0; c < 3; c++) eu[c] = dr_sample(A.seed, LM_DR_STREAM_RESET + LM_DR_RESET_ORIENTATION, e, key, (uint32_t)c, co.distribution, co.p0[c], co.p1[c]);
+          Q4 qe = quat_from_euler(eu[0], eu[1], eu[2]);
+          if (co.operation == LM_DR_ADDITIVE) qe = qmul(qe, F.q);      // in the world frame, after the nominal orientation
+          const float rn = rsqrtf(qe.w * qe.w + qe.x * qe.x + qe.y * qe.y + qe.z * qe.z);
+          F.q.w = qe.w * rn; F.q.x = qe.x * rn; F.q.y = qe.y * rn; F.q.z = qe.z * rn;
+        }
+      }
+      if (active) {      // the state this env starts its episode from (LM_PTR_DR_RESET_STATE), nominal resets included
+        float* rs = (float*)(A.reset_dr + 2);
+#pragma unroll
+        for (int a = 0; a < 3; a++) { rs[(size_t)jj[a] * N + env] = q[a]; rs[(size_t)(12 + jj[a]) * N + env] = qd[a]; }
+        if (limb == 0) {
+          rs[(size_t)24 * N + env] = F.p.x; rs[(size_t)25 * N + env] = F.p.y; rs[(size_t)26 * N + env] = F.p.z;
+          rs[(size_t)27 * N + env] = F.q.w; rs[(size_t)28 * N + env] = F.q.x; rs[(size_t)29 * N + env] = F.q.y; rs[(size_t)30 * N + env] = F.q.z;
+        }
+      }
+    }
   }
   // world -> body-coordinate twist
   {
@@ -1984,6 +2028,7 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
   ALLOC(h->d_cnt, LM_CNT_ROWS * N * sizeof(int64_t));
   ALLOC(h->d_drc, LM_DR_CNT_ROWS * N * sizeof(int64_t));
   ALLOC(h->d_dr_phys, LM_DR_PHYS_ROWS * N * sizeof(float));
+  if (h->dr_enabled) ALLOC(h->d_reset_dr, 2 * sizeof(lm_reset_dr) + LM_DR_RESET_ROWS * N * sizeof(float));      // zeros: all four channels off
   ALLOC(h->d_obs, N * (size_t)h->num_obs * sizeof(float));
   ALLOC(h->d_states, N * 93 * sizeof(float));
   ALLOC(h->d_rew, N * sizeof(float));
@@ -2014,7 +2059,7 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
 
 int lm_destroy(lm_engine* h) {
   if (!h) return LM_OK;
-  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats};
+  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_reset_dr, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   delete h;
   return LM_OK;
@@ -2034,7 +2079,7 @@ static StepArgs make_args(lm_engine* h, const float* actions, const float* goal_
   A.W.obs_buf = h->d_obs; A.W.states_buf = h->d_states; A.W.rew_buf = h->d_rew; A.W.terms = h->d_terms; A.W.acc = h->d_acc;
   A.W.stats = (char*)h->d_stats; A.W.extras = h->d_extras; A.W.out_extras = nullptr; A.W.split_block = h->split / ENVS_PER_WAVE; A.W.acc_rows = h->acc_rows;
   A.W.out_obs = out_obs; A.W.out_states = out_states; A.W.out_rew = out_rew; A.W.out_resets = out_resets;
-  A.N = h->N; A.split = h->split; A.seed = h->seed; A.skip_reset = 0; A.nsub = -1; A.drc = h->d_drc; A.dr_phys = h->d_dr_phys;
+  A.N = h->N; A.split = h->split; A.seed = h->seed; A.skip_reset = 0; A.nsub = -1; A.drc = h->d_drc; A.dr_phys = h->d_dr_phys; A.reset_dr = h->d_reset_dr;
   for (int t = 0; t < 2; t++) A.kind[t] = h->h_params[t].variant * 2 + (h->h_params[t].mode == LM_MODE_MANI ? 1 : 0);
   return A;
 }
@@ -2080,6 +2125,30 @@ int lm_post_physics(lm_engine* h, const float* actions, float* out_obs, float* o
   void (*kern)(StepArgs) = A.kind[0] >= 2 ? k_step_pd : k_step;
   hipLaunchKernelGGL(kern, dim3(h->nblocks), dim3(64), 0, s, A);
   HIPCHK(hipGetLastError());
+  return LM_OK;
+}
+
+int lm_set_reset_randomization(lm_engine* h, int block, const lm_reset_dr* rd) {
+  if (!h || !rd) return fail(LM_EINVAL, "lm_set_reset_randomization: null argument");
+  if (!h->dr_enabled || !h->d_reset_dr) return fail(LM_EINVAL, "lm_set_reset_randomization: the engine was created without dr_enabled");
+  if (block < 0 || block >= h->n_tasks) return fail(LM_EINVAL, "lm_set_reset_randomization: block must be 0 (or 1 on a two-task engine)");
+  CHECK_DEVICE(h, "lm_set_reset_randomization");
+  for (int c = 0; c < LM_DR_RESET_CHANNELS; c++) {
+    const lm_dr_channel& ch = rd->ch[c];
+    if (!ch.enabled) continue;
+    const int ncomp = (c == LM_DR_RESET_POSITION || c == LM_DR_RESET_ORIENTATION) ? 3 : 1;      // the joint channels read p0[0] / p1[0]
+    if (ch.operation < 0 || ch.operation > 2 || ch.distribution < 0 || ch.distribution > 2)
+      return fail(LM_EINVAL, "lm_set_reset_randomization: invalid operation / distribution");
+    if (ch.interval != 0) return fail(LM_EINVAL, "lm_set_reset_randomization: the reset-state channels are on_reset entries (interval 0)");
+    if (ch.operation == LM_DR_SCALING && (c == LM_DR_RESET_JOINT_VEL || c == LM_DR_RESET_ORIENTATION))
+      return fail(LM_EINVAL, "lm_set_reset_randomization: scaling makes no sense on the joint velocities (nominal 0) or on the orientation (a quaternion)");
+    for (int k = 0; k < ncomp; k++) {
+      if (!std::isfinite(ch.p0[k]) || !std::isfinite(ch.p1[k])) return fail(LM_EINVAL, "lm_set_reset_randomization: non-finite distribution parameters");
+      if (ch.distribution == LM_DR_LOGUNIFORM && !(ch.p0[k] > 0 && ch.p1[k] > 0))
+        return fail(LM_EINVAL, "lm_set_reset_randomization: log-uniform bounds must be positive");
+    }
+  }
+  HIPCHK(hipMemcpy(h->d_reset_dr + block, rd, sizeof(lm_reset_dr), hipMemcpyHostToDevice));
   return LM_OK;
 }
 
@@ -2148,6 +2217,7 @@ void* lm_ptr(lm_engine* h, int kind) {
     case LM_PTR_CNT: return h->d_cnt;
     case LM_PTR_DR_CNT: return h->d_drc;
     case LM_PTR_DR_PHYS: return h->d_dr_phys;
+    case LM_PTR_DR_RESET_STATE: return h->d_reset_dr ? (void*)(h->d_reset_dr + 2) : nullptr;
     case LM_PTR_OBS_BUF: h->view_obs = true; return h->d_obs;
     case LM_PTR_STATES_BUF: h->view_states = true; return h->d_states;
     case LM_PTR_REW_BUF: return h->d_rew;

@@ -66,6 +66,12 @@ DR_DISTRIBUTIONS = {"gaussian": 0, "normal": 0, "uniform": 1, "loguniform": 2, "
 # contact-material channels (include/lm_engine.h LM_DR_MATERIALS): kept out of `dr` (the oracle's parameter block has nine slots)
 DR_MAT_ROBOT, DR_MAT_OTHER = 0, 1
 DR_ON_STARTUP = -1                  # DRChannel.interval of an on_startup material entry: one draw per env for the engine's lifetime
+# reset-state channels (include/lm_engine.h LM_DR_RESET_*): the state an env is reset to, drawn in the step launch at a gated reset.
+# Kept out of `dr` too: they reach the engine through lm_set_reset_randomization, not through the parameter block
+DR_RESET_JOINT_POS, DR_RESET_JOINT_VEL, DR_RESET_POSITION, DR_RESET_ORIENTATION = range(4)
+DR_RESET_CHANNELS = 4
+DR_RESET_ROWS = 31                  # rows of Engine.dr_reset_state: q 12, qd 12, free-body position 3, quaternion (w, x, y, z) 4
+DR_STREAM_RESET = 12                # random streams 12..15, after the material streams 10, 11
 FRICTION_COMBINE = {"average": 0, "min": 1, "multiply": 2, "max": 3}      # PhysX's PxCombineMode order (LM_COMBINE_*)
 
 
@@ -93,6 +99,10 @@ def _no_dr():
 
 def _no_mat():
     return [DRChannel() for _ in range(2)]
+
+
+def _no_reset():
+    return [DRChannel() for _ in range(DR_RESET_CHANNELS)]
 
 
 @dataclass
@@ -188,6 +198,10 @@ class EngineParams:
     mat_mu_other: float = 1.0
     friction_combine: int = 0                           # FRICTION_COMBINE
     friction_scale: float = FRICTION_SCALE
+    # reset-state channels [joint_positions, joint_velocities, position, orientation]: on a reset that passes the dr_min_frequency
+    # gate the env starts from operation(nominal, draw) instead of init_q / zero joint velocity / the free body's init pose (the base in
+    # locomotion blocks, the plate in manipulation blocks).  on_reset only (interval 0); not part of the C parameter block
+    dr_reset: List[DRChannel] = field(default_factory=_no_reset)
     # ---- RobotOmni.take_action control mode (robot/base/robot.py:444-461), variant 0 only: 0 velocity (every task of the path), 1 position
     # (target a * act_scale rad with act_scale = pi, PD gains pd_kp / kd), 2 effort (torque a * act_scale N m with act_scale = torque limit)
     drive_mode: int = 0

@@ -18,10 +18,11 @@ _SO = os.environ.get("LM_ENGINE_SO", os.path.join(_CSRC, "liblm_engine.so"))    
 
 STATE_ROWS, CNT_ROWS, NUM_OBS, NUM_STATES, NUM_ACTIONS, NUM_EXTRAS, TABLE_FLOATS, TERM_ROWS, READBACK = 115, 6, 64, 93, 12, 13, 502, 11, 99
 DR_PHYS_ROWS, DR_PHYS_MU = 43, 42       # LM_DR_PHYS_ROWS, LM_DR_PHYS_MU
-PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS = range(10)
+DR_RESET_CHANNELS, DR_RESET_ROWS = 4, 31      # LM_DR_RESET_CHANNELS, LM_DR_RESET_ROWS
+PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE = range(11)
 
 # names of the exported C symbols (checked by tests/test_abi.py against include/lm_engine.h)
-EXPORTS = ["lm_create", "lm_destroy", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
+EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
            "lm_forward_kinematics", "lm_debug_dynamics", "lm_ptr", "lm_num_envs", "lm_num_obs", "lm_set_seed", "lm_last_error", "lm_version", "lm_abi_version",
            "lm_gnn_param_count", "lm_gnn_forward", "lm_mlp_param_count", "lm_mlp_forward", "lm_mlp_param_count_obs", "lm_mlp_forward_obs",
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy"]
@@ -35,6 +36,25 @@ CNT = dict(successes=0, consecutive_successes=1, goal_reset_buf=2, reset_buf=3, 
 class LmDrChannel(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("operation", C.c_int32), ("distribution", C.c_int32), ("interval", C.c_int32),
                 ("p0", C.c_float * 3), ("p1", C.c_float * 3)]
+
+
+class LmResetDr(C.Structure):
+    """lm_reset_dr: the four reset-state channels of one parameter block (joint_positions, joint_velocities, position, orientation)."""
+    _fields_ = [("ch", LmDrChannel * DR_RESET_CHANNELS)]
+
+
+def _fill_channel(dst, ch):
+    dst.enabled, dst.operation, dst.distribution, dst.interval = int(ch.enabled), int(ch.operation), int(ch.distribution), int(ch.interval)
+    for c in range(3):
+        dst.p0[c] = float(ch.p0[c]); dst.p1[c] = float(ch.p1[c])
+
+
+def make_reset_dr(ep) -> LmResetDr:
+    """EngineParams.dr_reset -> C struct (all channels off for a block that carries none)."""
+    r = LmResetDr()
+    for i, ch in enumerate(getattr(ep, "dr_reset", None) or []):
+        _fill_channel(r.ch[i], ch)
+    return r
 
 
 ABI_VERSION = 5          # LM_ABI_VERSION of include/lm_engine.h this mirror was written against
@@ -96,9 +116,7 @@ def make_params(ep, clip_obs: float = 5.0, clip_actions: float = 1.0) -> LmParam
         if name in ("dr", "dr_mat"):
             dst = getattr(p, name)
             for i, ch in enumerate(getattr(ep, name)):
-                dst[i].enabled, dst[i].operation, dst[i].distribution, dst[i].interval = int(ch.enabled), int(ch.operation), int(ch.distribution), int(ch.interval)
-                for c in range(3):
-                    dst[i].p0[c] = float(ch.p0[c]); dst[i].p1[c] = float(ch.p1[c])
+                _fill_channel(dst[i], ch)
             continue
         if name == "dr_mat_buckets":
             for i, k in enumerate(ep.dr_mat_buckets):
@@ -164,6 +182,7 @@ def load_library() -> C.CDLL:
     vp, fp, ip = C.c_void_p, C.c_void_p, C.c_int
     lib.lm_create.argtypes = [C.POINTER(vp), ip, C.c_void_p, C.POINTER(LmParams), ip, ip, C.c_uint32]
     lib.lm_destroy.argtypes = [vp]
+    lib.lm_set_reset_randomization.argtypes = [vp, ip, C.POINTER(LmResetDr)]
     lib.lm_step.argtypes = [vp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.lm_post_physics.argtypes = [vp, fp, fp, fp, fp, fp, fp, vp]
     lib.lm_reset_all.argtypes = [vp, vp]
@@ -227,6 +246,11 @@ class Engine:
             rc = self.lib.lm_create(C.byref(self._h), self.num_envs, table.ctypes.data_as(C.c_void_p), arr, len(params),
                                     int(split_env or 0), C.c_uint32(seed))
         self._check(rc)
+        for b, ep in enumerate(params):          # reset-state channels: handed over per block, before the first step
+            if any(ch.enabled for ch in (getattr(ep, "dr_reset", None) or [])):
+                rd = make_reset_dr(ep)
+                with torch.cuda.device(self.device):
+                    self._check(self.lib.lm_set_reset_randomization(self._h, b, C.byref(rd)))
         self.seed = int(seed) & 0xFFFFFFFF
         N = self.num_envs
         self.state = self._wrap(PTR_STATE, (STATE_ROWS, N), "<f4")
@@ -266,6 +290,17 @@ class Engine:
     @property
     def terms(self):
         return self._view(PTR_TERMS, (TERM_ROWS, self.num_envs))
+
+    @property
+    def dr_reset_state(self):
+        """float [31][N]: the state each env was last reset to by step() - q 12, qd 12, free-body position 3, quaternion (w, x, y, z) 4 -
+        nominal resets included.  Randomised engines only (dr_enabled)."""
+        if "dr_reset_state" not in self._views:
+            ptr = self.lib.lm_ptr(self._h, PTR_DR_RESET_STATE)
+            if not ptr:
+                raise EngineError("dr_reset_state: the engine was created without dr_enabled (no reset-state record)")
+            self._views["dr_reset_state"] = self.torch.as_tensor(_DevArray(ptr, (DR_RESET_ROWS, self.num_envs), "<f4", self), device=self.device)
+        return self._views["dr_reset_state"]
 
     @property
     def blowups(self) -> int:

@@ -24,6 +24,13 @@ Supported entries (everything the reference's YAMLs enable):
     rigid_prim_views.plate.material_properties         optional num_buckets: the contact friction of the feet / of the plate per env
                                                        (EngineParams.dr_mat).  Only the dynamic component enters; a
                                                        static or restitution component that would change warns (not modelled)
+    articulation_views.<robot>.joint_positions         on_reset, additive | scaling | direct, scalar parameters: the 12 driven joints' reset pose
+    articulation_views.<robot>.joint_velocities        on_reset, additive | direct, scalar parameters: their reset velocity (nominal 0)
+    articulation_views.<robot>.position                on_reset, additive | scaling | direct, per-component parameters: the base's reset position
+    articulation_views.<robot>.orientation             on_reset, additive | direct, per-component Euler angles (roll, pitch, yaw): its reset orientation
+    rigid_prim_views.plate.position / .orientation     the same for the plate of the manipulation blocks (the robot is fixed there)
+                                                       (EngineParams.dr_reset; DESIGN.md 3.6: drawn inside the step launch at every reset that
+                                                       passes min_frequency; no clamping to the joint ranges)
 Anything else (mass, density, material_properties of other views, stiffness ...) raises NotImplementedError when
 `randomize: True` - a silently ignored randomisation would be worse than a loud one."""
 from __future__ import annotations
@@ -33,8 +40,8 @@ from typing import List
 import numpy as np
 
 from ...engine_config import (DR_ACT_INTERVAL, DR_ACT_RESET, DR_BASE_FORCE, DR_CHANNELS, DR_DISTRIBUTIONS, DR_GRAVITY, DR_JOINT_DAMPING, DR_MAT_OTHER,
-                              DR_MAT_ROBOT, DR_MAX_EFFORT, DR_MAX_VELOCITY, DR_OBS_INTERVAL, DR_OBS_RESET, DR_ON_STARTUP, DR_OPERATIONS, MODE_MANI,
-                              DRChannel)
+                              DR_MAT_ROBOT, DR_MAX_EFFORT, DR_MAX_VELOCITY, DR_OBS_INTERVAL, DR_OBS_RESET, DR_ON_STARTUP, DR_OPERATIONS, DR_RESET_CHANNELS,
+                              DR_RESET_JOINT_POS, DR_RESET_JOINT_VEL, DR_RESET_ORIENTATION, DR_RESET_POSITION, MODE_LOCO, MODE_MANI, DRChannel)
 
 _ON_RESET_KEYS = ("operation", "distribution", "distribution_parameters")
 _ON_INTERVAL_KEYS = ("frequency_interval", "operation", "distribution", "distribution_parameters")
@@ -118,6 +125,37 @@ def _material_channel(where: str, entry: dict, trigger: str):
     return ch, buckets
 
 
+# reset-state attributes -> (channel, vector parameters, operations that make sense)
+_RESET_STATE = {"joint_positions": (DR_RESET_JOINT_POS, False, ("additive", "scaling", "direct")),
+                "joint_velocities": (DR_RESET_JOINT_VEL, False, ("additive", "direct")),
+                "position": (DR_RESET_POSITION, True, ("additive", "scaling", "direct")),
+                "orientation": (DR_RESET_ORIENTATION, True, ("additive", "direct"))}
+_RESET_STATE_WHY = {"joint_velocities": "the nominal joint velocity is 0, so scaling it changes nothing",
+                    "orientation": "the draw is three Euler angles turned into a quaternion, which is applied after the nominal one (additive) or "
+                                   "replaces it (direct); a quaternion is not scaled"}
+
+
+def _reset_state_channel(where: str, attribute: str, entry: dict) -> DRChannel:
+    """One reset-state entry (joint_positions / joint_velocities / position / orientation) -> DRChannel; on_reset is the only trigger."""
+    _, vector, ops = _RESET_STATE[attribute]
+    if entry is None:
+        raise ValueError(f"Randomization parameters for {where} is not provided.")
+    other = [t for t in ("on_interval", "on_startup") if t in entry]
+    if other or "on_reset" not in entry:
+        raise NotImplementedError(f"{where}: the reset state is drawn when an env is reset, so on_reset is its only trigger"
+                                  + (f" (got {', '.join(other)})" if other else ""))
+    e = entry["on_reset"]
+    if e is not None and "operation" in e and str(e["operation"]) in DR_OPERATIONS and str(e["operation"]) not in ops:
+        raise ValueError(f"{where} on_reset: operation {e['operation']!r} is refused: {_RESET_STATE_WHY[attribute]}")
+    ch = _channel(where, e or {}, "on_reset", vector)
+    n = 3 if vector else 1
+    if not (np.isfinite(ch.p0[:n]).all() and np.isfinite(ch.p1[:n]).all()):
+        raise ValueError(f"{where} on_reset: distribution_parameters must be finite")
+    if ch.distribution == DR_DISTRIBUTIONS["loguniform"] and not (min(ch.p0[:n]) > 0 and min(ch.p1[:n]) > 0):
+        raise ValueError(f"{where} on_reset: loguniform parameters must be positive")
+    return ch
+
+
 class Randomizer:
     def __init__(self, sim_config):
         self._cfg = sim_config.task_config
@@ -128,6 +166,9 @@ class Randomizer:
         self._channels: List[DRChannel] = [DRChannel() for _ in range(DR_CHANNELS)]
         self._mat_channels: List[DRChannel] = [DRChannel(), DRChannel()]          # [robot feet, plate] (EngineParams.dr_mat)
         self._mat_buckets: List[int] = [0, 0]
+        # reset-state channels per block mode (EngineParams.dr_reset): the joint entries go to both, position / orientation to the block
+        # whose free body they name (articulation_views.<robot>: the base of locomotion blocks; rigid_prim_views.plate: manipulation blocks)
+        self._reset_channels = {MODE_LOCO: [DRChannel() for _ in range(DR_RESET_CHANNELS)], MODE_MANI: [DRChannel() for _ in range(DR_RESET_CHANNELS)]}
         self._observations_dr_params = None
         self._actions_dr_params = None
         self.startup_scales = dict()          # (group, view) -> per-env factors drawn by apply_on_startup_domain_randomization
@@ -166,6 +207,8 @@ class Randomizer:
                 for attribute, entry in (attrs or {}).items():
                     if entry is None or "on_startup" not in entry or attribute == "material_properties":
                         continue          # material_properties on_startup is a channel of the engine (set_up_domain_randomization)
+                    if attribute in _RESET_STATE:
+                        continue          # reset-state entries: set_up_domain_randomization refuses every trigger but on_reset, with the reason
                     st = entry["on_startup"]
                     if not set(_ON_RESET_KEYS).issubset(st.keys()):          # randomize.py:75-77,104-106
                         raise ValueError(f"Please ensure the following randomization parameters for {view} {attribute} on_startup are provided: "
@@ -223,6 +266,12 @@ class Randomizer:
                         if attribute == "material_properties" and view == PLATE_VIEW:
                             self._set_up_material(("rigid_prim_views", view, attribute), entry, DR_MAT_OTHER)
                             continue
+                        if attribute in ("position", "orientation") and view == PLATE_VIEW:
+                            if not hasattr(task, "robot_manipulation"):
+                                raise NotImplementedError(f"rigid_prim_views.{view}.{attribute}: this task has no manipulation block, so there is no plate to "
+                                                          f"reset; the base's reset pose is articulation_views.<robot>.{attribute}")
+                            self._set_up_reset_state(("rigid_prim_views", view, attribute), entry, (MODE_MANI,))
+                            continue
                         if attribute != "force":
                             raise NotImplementedError(f"domain randomisation of rigid_prim_views.{view}.{attribute} is not implemented")
                         self._set_up_attribute(("rigid_prim_views", view, attribute), entry, DR_BASE_FORCE, vector=True)
@@ -237,6 +286,16 @@ class Randomizer:
                         if attribute == "joint_friction":          # the joint friction coefficient itself is not modelled: scaling it changes nothing
                             import warnings
                             warnings.warn(f"articulation_views.{view}.joint_friction: joint friction is not modelled by this engine; entry ignored")
+                            continue
+                        if attribute in _RESET_STATE:
+                            if attribute in ("position", "orientation"):
+                                if not hasattr(task, "robot_locomotion"):
+                                    raise NotImplementedError(f"articulation_views.{view}.{attribute}: the robot's base is fixed in a manipulation task; the "
+                                                              f"free body there is the plate (rigid_prim_views.{PLATE_VIEW}.{attribute})")
+                                modes = (MODE_LOCO,)
+                            else:
+                                modes = (MODE_LOCO, MODE_MANI)
+                            self._set_up_reset_state(("articulation_views", view, attribute), entry, modes)
                             continue
                         ch = {"max_efforts": DR_MAX_EFFORT, "joint_max_velocities": DR_MAX_VELOCITY, "damping": DR_JOINT_DAMPING}.get(attribute)
                         if ch is None:
@@ -268,6 +327,14 @@ class Randomizer:
                 self._channels[ch] = _channel(".".join(key), entry[trigger], trigger, vector)
                 self.active_domain_randomizations[key + (trigger,)] = np.array(entry[trigger]["distribution_parameters"])
 
+    def _set_up_reset_state(self, key, entry, modes):
+        """joint_positions / joint_velocities / position / orientation on_reset -> the reset-state channel of the blocks of `modes`."""
+        attribute = key[-1]
+        ch = _reset_state_channel(".".join(key), attribute, entry)
+        for m in modes:
+            self._reset_channels[m][_RESET_STATE[attribute][0]] = ch
+        self.active_domain_randomizations[key + ("on_reset",)] = np.array(entry["on_reset"]["distribution_parameters"])
+
     def _set_up_material(self, key, entry, ch):
         """material_properties of the robot (ch = DR_MAT_ROBOT) or the plate (DR_MAT_OTHER): one trigger, dynamic component into the engine."""
         where = ".".join(key)
@@ -297,7 +364,8 @@ class Randomizer:
         mat = list(self._mat_channels); buckets = list(self._mat_buckets)
         if mode != MODE_MANI:
             mat[DR_MAT_OTHER] = DRChannel(); buckets[DR_MAT_OTHER] = 0
-        return dict(dr_enabled=1, dr_min_frequency=int(self.min_frequency), dr=list(self._channels), dr_mat=mat, dr_mat_buckets=buckets)
+        return dict(dr_enabled=1, dr_min_frequency=int(self.min_frequency), dr=list(self._channels), dr_mat=mat, dr_mat_buckets=buckets,
+                    dr_reset=list(self._reset_channels[MODE_MANI if mode == MODE_MANI else MODE_LOCO]))
 
     # The wrapper calls these two exactly where the reference does (vec_env_rlgames.py:56-58,70-72).  The noise has already been /
     # will be applied inside lm_step with the reference's counter semantics (randomize.py:212-306), so they hand the tensor through.

@@ -1,5 +1,7 @@
 """Cost of domain randomisation inside the step launch: k_step vs k_step_dr (YAML block of QuadrupedPoseControl.yaml) at 4096 envs, and what
-the contact-material channel adds to k_step_dr (the same block + the feet's material_properties, redrawn every step in 64 buckets)."""
+the contact-material channel adds to k_step_dr (the same block + the feet's material_properties, redrawn every step in 64 buckets), and what
+the four reset-state channels add (the same block + joint_positions / joint_velocities / position / orientation at the reference's amplitudes,
+min_frequency 0: every reset draws; and behind the YAML's min_frequency, which outlasts the run: no reset draws).  `resets_per_step` is the mean number of envs reset per timed step of each leg."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -8,17 +10,29 @@ import locomanipulationrl_amd as lm
 res = {}
 MATERIAL = {"articulation_views": {"robot_view": {"material_properties": {"on_interval": dict(
     frequency_interval=1, operation="scaling", distribution="uniform", distribution_parameters=[[1.0, 0.6, 1.0], [1.0, 1.4, 1.0]], num_buckets=64)}}}}
+_R = lambda prm: {"on_reset": dict(operation="additive", distribution="uniform", distribution_parameters=prm)}
+RESET_STATE = {"articulation_views": {"robot_view": {"joint_positions": _R([-0.1, 0.1]), "joint_velocities": _R([-0.1, 0.1]),
+                                                     "position": _R([[-0.05, -0.05, 0.0], [0.05, 0.05, 0.1]]), "orientation": _R([[-0.1, -0.1, -1.2], [0.1, 0.1, 1.2]])}}}
+resets = {}
 for name, ov in (("plain", None), ("randomised", {"task": {"domain_randomization": {"randomize": True}}}),
-                 ("randomised_material", {"task": {"domain_randomization": {"randomize": True, "randomization_params": MATERIAL}}})):
+                 ("randomised_material", {"task": {"domain_randomization": {"randomize": True, "randomization_params": MATERIAL}}}),
+                 ("randomised_min_frequency_0", {"task": {"domain_randomization": {"randomize": True, "min_frequency": 0}}}),
+                 ("randomised_reset_state", {"task": {"domain_randomization": {"randomize": True, "min_frequency": 0, "randomization_params": RESET_STATE}}}),
+                 # the same channels behind a gate that never opens (the YAML's min_frequency outlasts the run): what they cost the steps that do not draw
+                 ("randomised_reset_state_gate_closed", {"task": {"domain_randomization": {"randomize": True, "randomization_params": RESET_STATE}}})):
     env = lm.make_env("QuadrupedPoseControl", num_envs=4096, overrides=ov)
     e = env._task.engine; N = 4096
     g = torch.Generator(device="cuda").manual_seed(0)
     pool = [torch.rand(N, 12, device="cuda", generator=g) * 2 - 1 for _ in range(16)]
     o = (torch.empty(N, 64, device="cuda"), torch.empty(N, 93, device="cuda"), torch.empty(N, device="cuda"), torch.empty(N, dtype=torch.int64, device="cuda"), torch.empty(13, device="cuda"))
     for t in range(50): e.step(pool[t % 16], None, *o)
-    torch.cuda.synchronize(); t0 = time.perf_counter()
+    torch.cuda.synchronize(); ep0 = int(e.cnt[5].sum().item()); t0 = time.perf_counter()
     for t in range(500): e.step(pool[t % 16], None, *o)
     torch.cuda.synchronize(); res[name] = (time.perf_counter() - t0) / 500 * 1e6
+    resets[name] = (int(e.cnt[5].sum().item()) - ep0) / 500
     env.close()
 print(json.dumps({"us_per_step": res, "overhead": res["randomised"] / res["plain"] - 1,
-                  "material_overhead_on_k_step_dr": res["randomised_material"] / res["randomised"] - 1}))
+                  "material_overhead_on_k_step_dr": res["randomised_material"] / res["randomised"] - 1,
+                  "reset_state_overhead_on_k_step_dr": res["randomised_reset_state"] / res["randomised_min_frequency_0"] - 1,
+                  "reset_state_gate_closed_overhead_on_k_step_dr": res["randomised_reset_state_gate_closed"] / res["randomised"] - 1,
+                  "resets_per_step": resets}))
