@@ -97,6 +97,29 @@ enum { LM_COMBINE_AVERAGE = 0, LM_COMBINE_MIN = 1, LM_COMBINE_MULTIPLY = 2, LM_C
 enum { LM_DR_RESET_JOINT_POS = 0, LM_DR_RESET_JOINT_VEL = 1, LM_DR_RESET_POSITION = 2, LM_DR_RESET_ORIENTATION = 3 };
 typedef struct lm_reset_dr { lm_dr_channel ch[LM_DR_RESET_CHANNELS]; } lm_reset_dr;
 #define LM_DR_RESET_ROWS 31  /* float [row][N]: q 12, qd 12, free-body position 3, free-body quaternion (w, x, y, z) 4 */
+/* Mass channels: per-env masses of the plate and of the robot's 21 bodies, drawn inside lm_step for the control step (constant
+ * over its sub-steps).  They live in a struct of their own, handed over with lm_set_mass_randomization, so that lm_params keeps its layout.
+ * interval: >= 1 on_interval, 0 on_reset (gated by dr_min_frequency; nominal before the first gated reset), LM_DR_ON_STARTUP: one draw per env,
+ * keyed by (seed, stream, env, component) only.  Scalar parameters p0[0] / p1[0] for the two plate channels; the body channel reads body_p0 /
+ * body_p1, one pair per body in TABLE ORDER: 0 = hub, 1 + 5 limb + j with j over (shell, link4, link3, link1, link2); that index is also the
+ * component of the draw.
+ *   LM_DR_MASS_PLATE          the plate's mass.  Mass only: COM and inertia about the COM stay (what setting a mass through a simulator's tensor
+ *                             API does); the spatial inertia about the plate origin changes through the parallel-axis term
+ *   LM_DR_MASS_PLATE_DENSITY  a factor s on the plate's mass AND its inertia about the COM; LM_DR_ON_STARTUP + LM_DR_SCALING only (the URDF gives
+ *                             mass and inertia but no volume: no nominal density exists).  Applied first: the nominal of LM_DR_MASS_PLATE is then
+ *                             s x plate_mass
+ *   LM_DR_MASS_BODIES         21 components, the masses of the hub and the limb bodies; mass only, as above
+ * A drawn mass (and s) is floored at LM_DR_MASS_FLOOR x its nominal, so that a gaussian tail cannot produce a non-positive mass; a bounded
+ * distribution (uniform, loguniform) whose range reaches a non-positive mass is refused by lm_set_mass_randomization.  The plate channels exist
+ * on manipulation blocks only; in a manipulation block the base is fixed, so the hub's draw is recorded but has no effect.  The random streams
+ * are 16 (plate mass), 17 (plate density), 18 (body masses). */
+#define LM_DR_MASS_CHANNELS 3
+enum { LM_DR_MASS_PLATE = 0, LM_DR_MASS_PLATE_DENSITY = 1, LM_DR_MASS_BODIES = 2 };
+#define LM_NUM_BODIES 21
+#define LM_DR_MASS_FLOOR 0.05f
+typedef struct lm_mass_dr { lm_dr_channel ch[LM_DR_MASS_CHANNELS];
+                            float body_p0[LM_NUM_BODIES], body_p1[LM_NUM_BODIES]; /* table order */ } lm_mass_dr;
+#define LM_DR_MASS_ROWS 23   /* float [row][N]: plate mass, plate inertia factor, 21 body masses (table order): what the last step used, floored */
 
 typedef struct lm_params {
   int32_t abi_version;     /* LM_ABI_VERSION of the header the caller was compiled against */
@@ -174,8 +197,10 @@ typedef enum {
   LM_PTR_DR_CNT = 8,    /* int64 [LM_DR_CNT_ROWS][N]  domain-randomisation counters */
   LM_PTR_DR_PHYS = 9,   /* float [LM_DR_PHYS_ROWS][N]  attributes sampled for the last step: max efforts 12, max joint velocities 12,
                            gravity 3, base force 3, joint damping 12, mu_env 1 (row LM_DR_PHYS_MU) */
-  LM_PTR_DR_RESET_STATE = 10 /* float [LM_DR_RESET_ROWS][N]  the state each env was last reset to by lm_step (nominal resets included);
+  LM_PTR_DR_RESET_STATE = 10, /* float [LM_DR_RESET_ROWS][N]  the state each env was last reset to by lm_step (nominal resets included);
                            randomised engines only (NULL otherwise) */
+  LM_PTR_DR_MASS = 11   /* float [LM_DR_MASS_ROWS][N]  plate mass, plate inertia factor and the 21 body masses (table order) the last step used;
+                           the nominal values until a mass channel draws; randomised engines only (NULL otherwise) */
 } lm_ptr_kind;
 
 /* Create an engine for n_envs environments on the current HIP device.
@@ -199,6 +224,14 @@ int lm_destroy(lm_engine* h);
  * log-uniform with non-positive bounds, or non-finite parameters.  Synchronous (a blocking copy): call it before the first step and not
  * while a graph that contains lm_step is being captured. */
 int lm_set_reset_randomization(lm_engine* h, int block, const lm_reset_dr* rd);
+
+/* Mass randomisation of parameter block `block` (0, or 1 on a two-task engine): validates *md and copies it to device memory owned by the
+ * handle; later lm_step launches draw from it (see LM_DR_MASS_CHANNELS above).  All three channels are off after lm_create.
+ * LM_EINVAL: engine without dr_enabled; block out of range; an enabled channel with a bad operation / distribution / interval (below
+ * LM_DR_ON_STARTUP); the density channel with anything but LM_DR_ON_STARTUP + LM_DR_SCALING; non-finite parameters; log-uniform with
+ * non-positive bounds; a uniform / log-uniform range that reaches a non-positive mass (or density factor); a plate channel on a locomotion
+ * block.  Synchronous (a blocking copy): call it before the first step and not while a graph that contains lm_step is being captured. */
+int lm_set_mass_randomization(lm_engine* h, int block, const lm_mass_dr* md);
 
 /* One VecEnvRLGames.step(): reset flagged envs, clamp + apply actions, controlFrequencyInv physics
  * sub-steps, observations / reward / termination.  (vec_env_rlgames.py:56-79)

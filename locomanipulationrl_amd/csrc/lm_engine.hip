@@ -103,6 +103,8 @@ struct lm_engine {
   float* d_table;
   float* d_state; int64_t* d_cnt; int64_t* d_drc; float* d_dr_phys; int dr_enabled;
   lm_reset_dr* d_reset_dr; // randomised engines: the reset-state channels of the two blocks, followed by float [LM_DR_RESET_ROWS][N] (LM_PTR_DR_RESET_STATE)
+  lm_mass_dr* d_mass_dr;   // randomised engines: the mass channels of the two blocks, followed by float [LM_DR_MASS_ROWS][N] (LM_PTR_DR_MASS)
+  float h_body_mass[LM_NUM_BODIES];      // nominal body masses in table order (what lm_set_mass_randomization checks ranges against)
   float *d_obs, *d_states, *d_rew, *d_extras, *d_terms; long long* d_acc; int acc_rows;
   bool view_obs, view_states, view_terms;      // lm_ptr() handed out obs_buf / states_buf / the reward terms: lm_step keeps them current from then on
   char* d_stats;           // int64 {num_successes, num_resets} x {all, first task, second task}; float success_rate x 3 at byte 48;
@@ -181,7 +183,19 @@ LM_DEV float dr_material(const lm_dr_channel& ch, int buckets, uint32_t seed, ui
 LM_DEV float friction_combine(int mode, float a, float b) {
   return mode == LM_COMBINE_AVERAGE ? 0.5f * (a + b) : mode == LM_COMBINE_MIN ? fminf(a, b) : mode == LM_COMBINE_MULTIPLY ? a * b : fmaxf(a, b);
 }
-struct DrPhys { float tmax[3], vmax[3], cj[3]; V3 g, f; float mu; };      // this lane's three joints; gravity (world); base-link force (world); contact mu
+// mass channel (include/lm_engine.h, LM_DR_MASS_CHANNELS): operation(nominal, draw) floored at LM_DR_MASS_FLOOR x nominal.  Keys as for the
+// material channels; `comp` is the component of the draw (the body's index in table order), p0 / p1 its parameters
+#define LM_DR_STREAM_MASS 16U     // streams 16 (plate mass), 17 (plate density), 18 (body masses)
+LM_DEV float dr_mass(const lm_dr_channel& ch, uint32_t seed, uint32_t stream, int env, uint32_t dr_step, uint32_t reset_key, uint32_t comp, float p0, float p1, float base) {
+  if (!ch.enabled) return base;
+  const uint32_t key = ch.interval > 0 ? dr_step / (uint32_t)ch.interval : (ch.interval < 0 ? 0U : reset_key);
+  if (ch.interval == 0 && key == 0) return base;
+  return fmaxf(dr_apply(ch.operation, base, dr_sample(seed, stream, (uint32_t)env, key, comp, ch.distribution, p0, p1)), LM_DR_MASS_FLOOR * base);
+}
+struct DrPhys { float tmax[3], vmax[3], cj[3]; V3 g, f; float mu;      // this lane's three joints; gravity (world); base-link force (world); contact mu
+                // mass channels: wave-uniform switches (bodies / plate); masses of the shell, (link4 | link1), (link3 | link2) and the hub; the plate's
+                // mass and the factor on its inertia about the COM.  Read only where the matching switch is on
+                int mb_on, mp_on; float m_s; f2 m_41, m_32; float m_hub, m_plate, s_plate; };
 LM_DEV Q4 quat_from_euler(float roll, float pitch, float yaw) {
   float sy, cy, sr, cr, sp, cp;
   sincosf(yaw * 0.5f, &sy, &cy); sincosf(roll * 0.5f, &sr, &cr); sincosf(pitch * 0.5f, &sp, &cp);
@@ -293,10 +307,14 @@ struct LimbDyn {
 LM_DEV V3 sel(bool c, V3 a, V3 b) { return v3(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z); }
 LM_DEV SV sel(bool c, SV a, SV b) { return sv(sel(c, a.w, b.w), sel(c, a.v, b.v)); }
 
-LM_DEV void limb_dynamics(const float* tl, const LimbKin& K, const float qd[3], SV v0, SV avp0, LimbDyn& D) {
+// MASS = 1 (the randomised kernels with the body-mass channel on): the masses of the five bodies come from the caller instead of the table;
+// COM and inertia about the COM stay the table's
+template <int MASS = 0>
+LM_DEV void limb_dynamics(const float* tl, const LimbKin& K, const float qd[3], SV v0, SV avp0, LimbDyn& D, float m_s = 0.f, f2 m_41 = f2{0.f, 0.f}, f2 m_32 = f2{0.f, 0.f}) {
   const f2* tp = reinterpret_cast<const f2*>(tl);
-  const SI Is = place_inertia<float>(tl + T_I0, K.Rs, K.os);
-  const SIP I41 = place_inertia<f2>(tp + T_Q1 / 2, K.R41, K.o41), I32 = place_inertia<f2>(tp + T_Q2 / 2, K.R32, K.o32);
+  const SI Is = MASS ? place_inertia_m<float>(tl + T_I0, m_s, K.Rs, K.os) : place_inertia<float>(tl + T_I0, K.Rs, K.os);
+  const SIP I41 = MASS ? place_inertia_m<f2>(tp + T_Q1 / 2, m_41, K.R41, K.o41) : place_inertia<f2>(tp + T_Q1 / 2, K.R41, K.o41),
+            I32 = MASS ? place_inertia_m<f2>(tp + T_Q2 / 2, m_32, K.R32, K.o32) : place_inertia<f2>(tp + T_Q2 / 2, K.R32, K.o32);
   // velocities / velocity-product accelerations down the two chains
   const SV j1 = qd[0] * K.s1; const SVP j23 = mk2(qd[1], qd[2]) * K.s23, jp = mk2(K.pd, -K.pd) * K.sp12;
   const SV vs = v0 + j1; const SVP v41 = bc(vs) + j23, v32 = v41 + jp;
@@ -542,6 +560,27 @@ extern "C" void lm_dbg_pass2_read(unsigned int* out, int clear) {
 }
 #endif
 
+// Per-env plate inertia of the randomised kernels (mass channels): the plate's inertia about its COM is diagonal, so the inverse of its spatial
+// inertia about the plate origin is  X^-1 diag(1 / I_com, 1 / m) X^-T  with X the shift by the COM: seven numbers instead of a 6 x 6 matrix.
+// For a wrench (n about the origin, f):  alpha = (n - c x f) / I_com,  a_origin = f / m + c x alpha
+template <class T> struct PlateInvT { V3T<T> ii, c; T im; };
+LM_DEV PlateInvT<float> plate_inv(const lm_params* __restrict__ P, float m, float s) {
+  PlateInvT<float> Q; Q.ii = v3(1.0f / (s * P->plate_inertia[0]), 1.0f / (s * P->plate_inertia[1]), 1.0f / (s * P->plate_inertia[2]));
+  Q.c = v3(P->plate_com[0], P->plate_com[1], P->plate_com[2]); Q.im = 1.0f / m; return Q;
+}
+template <class T> LM_DEV void plate_inv_apply(const PlateInvT<T>& Q, V3T<T> n, V3T<T> f, V3T<T>& al, V3T<T>& a) {
+  const V3T<T> nc = n - cross(Q.c, f);
+  al = v3t<T>(nc.x * Q.ii.x, nc.y * Q.ii.y, nc.z * Q.ii.z);
+  a = fma3(Q.im, f, cross(Q.c, al));
+}
+LM_DEV SI plate_inertia_env(const lm_params* __restrict__ P, float m, float s) {      // spatial inertia about the plate origin from (m, COM, s x I_com)
+  const V3 c = v3(P->plate_com[0], P->plate_com[1], P->plate_com[2]); const float cc = dot(c, c);
+  SI I; I.m = m; I.h = m * c;
+  I.xx = fmaf(m, cc - c.x * c.x, s * P->plate_inertia[0]); I.yy = fmaf(m, cc - c.y * c.y, s * P->plate_inertia[1]); I.zz = fmaf(m, cc - c.z * c.z, s * P->plate_inertia[2]);
+  I.xy = -m * c.x * c.y; I.xz = -m * c.x * c.z; I.yz = -m * c.y * c.z;
+  return I;
+}
+
 // One physics sub-step of one env (4 lanes).  MODE 0: F is the robot base.  MODE 1: F is the plate, the
 // robot base is fixed at (Rb, pb).
 template <int MODE, int VAR, int DR>
@@ -551,6 +590,8 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
   const float cjv[3] = {VAR ? (DR ? X.cj[0] : P->joint_damping) : 0.f, VAR ? (DR ? X.cj[1] : P->joint_damping) : 0.f, VAR ? (DR ? X.cj[2] : P->joint_damping) : 0.f};
   const float tmax[3] = {DR ? X.tmax[0] : P->tau_max, DR ? X.tmax[1] : P->tau_max, DR ? X.tmax[2] : P->tau_max};
   const float mu_dr = DR ? X.mu : 0.f;      // the DrPhys X is shadowed by the contact rows inside the pass loop
+  const bool mp_on = DR && MODE == 1 && X.mp_on;      // a plate mass channel is on (wave-uniform): per-env plate inertia instead of plate_si / plate_phi
+  const float m_plate = mp_on ? X.m_plate : 0.f, s_plate = mp_on ? X.s_plate : 0.f;
   M3 Rf = quat_to_mat(F.q.w, F.q.x, F.q.y, F.q.z);
   float bn;
   {
@@ -558,12 +599,22 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
     if (MODE == 0) { Rb = Rf; pb = F.p; v0 = F.u; } else { Rb = Rfix; pb = pfix; v0 = sv(v3(0, 0, 0), v3(0, 0, 0)); }
     SV avp0 = sv(v3(0, 0, 0), DR ? mulT(Rb, -X.g) : P->gravity * row2(Rb));      // fictitious acceleration = -gravity
     LimbKin K; limb_kinematics(tl, q, qd, K);
-    LimbDyn D; limb_dynamics(tl, K, qd, v0, avp0, D);
+    LimbDyn D;
+    if (DR && X.mb_on) limb_dynamics<1>(tl, K, qd, v0, avp0, D, X.m_s, X.m_41, X.m_32);      // body-mass channel on (wave-uniform): per-env masses
+    else limb_dynamics(tl, K, qd, v0, avp0, D);
     LM_STAMP(1);
     if (MODE == 0) {
       // the hub body itself rides on limb 0's contribution to the quad reductions
       const float m0 = (limb == 0) ? 1.f : 0.f;
       SI I0 = hub_inertia(th);
+      if (DR && X.mb_on) {
+        // per-env hub mass m': the COM c = h / m and the inertia about it stay, so I_O' = I_O + (m' - m) (|c|^2 1 - c c^T) and h' = h m' / m.
+        // In this form m' = m gives the table's values back bit for bit
+        const V3 c = (1.0f / I0.m) * I0.h; const float dm = X.m_hub - I0.m, cc = dot(c, c);
+        I0.xx = fmaf(dm, cc - c.x * c.x, I0.xx); I0.yy = fmaf(dm, cc - c.y * c.y, I0.yy); I0.zz = fmaf(dm, cc - c.z * c.z, I0.zz);
+        I0.xy = fmaf(dm, -(c.x * c.y), I0.xy); I0.xz = fmaf(dm, -(c.x * c.z), I0.xz); I0.yz = fmaf(dm, -(c.y * c.z), I0.yz);
+        I0.h = (X.m_hub / I0.m) * I0.h; I0.m = X.m_hub;
+      }
       const V3 com0 = (1.0f / I0.m) * I0.h;
       I0.m *= m0; I0.h = m0 * I0.h; I0.xx *= m0; I0.yy *= m0; I0.zz *= m0; I0.xy *= m0; I0.xz *= m0; I0.yz *= m0;
       D.Isc = D.Isc + I0;
@@ -597,17 +648,29 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
       V3 a0 = v3(0, 0, sg), a1 = v3(1, 0, 0), a2 = v3(0, sg, 0);
       SV Tp0 = sv(-cross(y0, a0), -a0), Tp1 = sv(-cross(y0, a1), -a1), Tp2 = sv(-cross(y0, a2), -a2);
       // plate free motion
-      SI Ip = load_si(P->plate_si);
-      SV hp = fcross(F.u, Ip * F.u);
-      V3 fg = DR ? P->plate_mass * mulT(Rf, X.g) : (-P->plate_mass * P->gravity) * row2(Rf);
-      V3 c = v3(P->plate_com[0], P->plate_com[1], P->plate_com[2]);
-      hp = hp - sv(cross(c, fg), fg);
-      float Ph[6][6];
+      SV up_free;
+      if (mp_on) {      // per-env plate mass / inertia factor
+        const V3 c = v3(P->plate_com[0], P->plate_com[1], P->plate_com[2]);
+        const SI Ip = plate_inertia_env(P, m_plate, s_plate);
+        SV hp = fcross(F.u, Ip * F.u);
+        const V3 fg = m_plate * mulT(Rf, X.g);
+        hp = hp - sv(cross(c, fg), fg);
+        const PlateInvT<float> Q = plate_inv(P, m_plate, s_plate);
+        V3 al, ac; plate_inv_apply<float>(Q, hp.w, hp.v, al, ac);
+        up_free = F.u - dt * sv(al, ac);
+      } else {
+        SI Ip = load_si(P->plate_si);
+        SV hp = fcross(F.u, Ip * F.u);
+        V3 fg = DR ? P->plate_mass * mulT(Rf, X.g) : (-P->plate_mass * P->gravity) * row2(Rf);
+        V3 c = v3(P->plate_com[0], P->plate_com[1], P->plate_com[2]);
+        hp = hp - sv(cross(c, fg), fg);
+        float Ph[6][6];
 #pragma unroll
-      for (int i = 0; i < 6; i++)
+        for (int i = 0; i < 6; i++)
 #pragma unroll
-        for (int j = 0; j < 6; j++) Ph[i][j] = P->plate_phi[6 * i + j];
-      SV up_free = F.u - dt * mul66(Ph, hp);
+          for (int j = 0; j < 6; j++) Ph[i][j] = P->plate_phi[6 * i + j];
+        up_free = F.u - dt * mul66(Ph, hp);
+      }
       // pass-invariant contact rows in the four-vector layout: slots 10-12 (up_free[i] | Tp0[i]), slots 13-15 (Tp1[i] | Tp2[i])
       St.put(10, up_free.w.x, Tp0.w.x, up_free.w.y, Tp0.w.y); St.put(11, up_free.w.z, Tp0.w.z, up_free.v.x, Tp0.v.x); St.put(12, up_free.v.y, Tp0.v.y, up_free.v.z, Tp0.v.z);
       St.put(13, Tp1.w.x, Tp2.w.x, Tp1.w.y, Tp2.w.y); St.put(14, Tp1.w.z, Tp2.w.z, Tp1.v.x, Tp2.v.x); St.put(15, Tp1.v.y, Tp2.v.y, Tp1.v.z, Tp2.v.z);
@@ -738,6 +801,16 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
       qdd[0] = Hi[0] * r[0] + Hi[1] * r[1] + Hi[2] * r[2]; qdd[1] = Hi[1] * r[0] + Hi[3] * r[1] + Hi[4] * r[2]; qdd[2] = Hi[2] * r[0] + Hi[4] * r[1] + Hi[5] * r[2];
 #pragma unroll
       for (int i = 0; i < 6; i++) { v0f[i] = PB[i].p.x; T[i] = PB[i]; }
+      if (mp_on) {
+        // B = Phi' T with this env's plate mass / inertia factor, through the COM (plate_inv_apply), both halves of the four-vector layout
+        const PlateInvT<float> Q1 = plate_inv(P, m_plate, s_plate);
+        PlateInvT<f2> Q; Q.ii = bc(Q1.ii); Q.c = bc(Q1.c); Q.im = sp2(Q1.im);
+        V3P al, ac;
+        plate_inv_apply<f2>(Q, v3(T[0].p, T[1].p, T[2].p), v3(T[3].p, T[4].p, T[5].p), al, ac);
+        X[0].p = al.x; X[1].p = al.y; X[2].p = al.z; X[3].p = ac.x; X[4].p = ac.y; X[5].p = ac.z;
+        plate_inv_apply<f2>(Q, v3(T[0].q, T[1].q, T[2].q), v3(T[3].q, T[4].q, T[5].q), al, ac);
+        X[0].q = al.x; X[1].q = al.y; X[2].q = al.z; X[3].q = ac.x; X[4].q = ac.y; X[5].q = ac.z;
+      } else {
       // B = Phi T with the plate's constant inverse inertia
 #pragma unroll
       for (int i = 0; i < 6; i++) {
@@ -745,6 +818,7 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
 #pragma unroll
         for (int j = 0; j < 6; j++) { const f2 ph = sp2(P->plate_phi[6 * i + j]); bp = fma_(ph, T[j].p, bp); bq = fma_(ph, T[j].q, bq); }
         X[i].p = bp; X[i].q = bq;
+      }
       }
     }
 #pragma unroll
@@ -1188,6 +1262,8 @@ struct StepArgs {
                     // arguments, so the first loads of the step do not wait for a round trip to the parameter block
   const lm_reset_dr* reset_dr;      // reset-state channels of the two blocks, followed by float [LM_DR_RESET_ROWS][N]: the state each env was last
                                     // reset to (k_step_dr / k_step_dr_pd only; kept last so that no other member moves)
+  const lm_mass_dr* mass_dr;        // mass channels of the two blocks, followed by float [LM_DR_MASS_ROWS][N]: the masses the last step used
+                                    // (k_step_dr / k_step_dr_pd only; appended for the same reason)
 };
 
 template <int MODE, int VAR, int DR, int DEFER = 0>
@@ -1251,6 +1327,36 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
       const float fr = dr_material(mr, P->dr_mat_buckets[LM_DR_MAT_ROBOT], A.seed, LM_DR_STREAM_MAT + LM_DR_MAT_ROBOT, env, dr_step, (uint32_t)dr_reset_key, P->mat_mu_robot);
       const float fo = dr_material(mo, P->dr_mat_buckets[LM_DR_MAT_OTHER], A.seed, LM_DR_STREAM_MAT + LM_DR_MAT_OTHER, env, dr_step, (uint32_t)dr_reset_key, P->mat_mu_other);
       X.mu = fmaxf(P->friction_scale * friction_combine(P->friction_combine, fr, fo), 0.f);
+    }
+    // mass channels: this lane's five limb bodies, the hub and, in a manipulation block, the plate.  The switches are
+    // wave-uniform (one parameter block per wavefront): with all channels off nothing below runs and the sub-steps take the table's path
+    {
+      const lm_mass_dr* MD = A.mass_dr + ((env0 >= A.split) ? 1 : 0);
+      const lm_dr_channel& cb = MD->ch[LM_DR_MASS_BODIES];
+      X.mb_on = cb.enabled;
+      X.mp_on = (MODE == 1 && (MD->ch[LM_DR_MASS_PLATE].enabled || MD->ch[LM_DR_MASS_PLATE_DENSITY].enabled)) ? 1 : 0;
+      float* mrec = (float*)(A.mass_dr + 2);
+      if (X.mb_on) {
+        const float* tn = A.table + HUB_FLOATS + limb * LIMB_STRIDE;      // nominal masses: the device table in memory (LDS is not filled yet)
+        const float nom[5] = {tn[T_I0], tn[T_Q1], tn[T_Q2], tn[T_Q1 + 1], tn[T_Q2 + 1]};      // shell, link4, link3, link1, link2
+        const int c0 = 1 + 5 * limb; float mm[5];
+#pragma unroll
+        for (int j = 0; j < 5; j++)
+          mm[j] = dr_mass(cb, A.seed, LM_DR_STREAM_MASS + LM_DR_MASS_BODIES, env, dr_step, (uint32_t)dr_reset_key, (uint32_t)(c0 + j), MD->body_p0[c0 + j], MD->body_p1[c0 + j], nom[j]);
+        X.m_s = mm[0]; X.m_41 = mk2(mm[1], mm[3]); X.m_32 = mk2(mm[2], mm[4]);
+        X.m_hub = dr_mass(cb, A.seed, LM_DR_STREAM_MASS + LM_DR_MASS_BODIES, env, dr_step, (uint32_t)dr_reset_key, 0U, MD->body_p0[0], MD->body_p1[0], A.table[0]);
+        if (active) {
+#pragma unroll
+          for (int j = 0; j < 5; j++) mrec[(size_t)(2 + c0 + j) * N + env] = mm[j];
+          if (limb == 0) mrec[(size_t)2 * N + env] = X.m_hub;
+        }
+      }
+      if (MODE == 1 && X.mp_on) {
+        const lm_dr_channel& cm = MD->ch[LM_DR_MASS_PLATE]; const lm_dr_channel& cd = MD->ch[LM_DR_MASS_PLATE_DENSITY];
+        X.s_plate = dr_mass(cd, A.seed, LM_DR_STREAM_MASS + LM_DR_MASS_PLATE_DENSITY, env, dr_step, (uint32_t)dr_reset_key, 0U, cd.p0[0], cd.p1[0], 1.0f);
+        X.m_plate = dr_mass(cm, A.seed, LM_DR_STREAM_MASS + LM_DR_MASS_PLATE, env, dr_step, (uint32_t)dr_reset_key, 0U, cm.p0[0], cm.p1[0], X.s_plate * P->plate_mass);
+        if (active && limb == 0) { mrec[env] = X.m_plate; mrec[(size_t)N + env] = X.s_plate; }
+      }
     }
     if (active) {
       float* ph = A.dr_phys;
@@ -2029,6 +2135,7 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
   ALLOC(h->d_drc, LM_DR_CNT_ROWS * N * sizeof(int64_t));
   ALLOC(h->d_dr_phys, LM_DR_PHYS_ROWS * N * sizeof(float));
   if (h->dr_enabled) ALLOC(h->d_reset_dr, 2 * sizeof(lm_reset_dr) + LM_DR_RESET_ROWS * N * sizeof(float));      // zeros: all four channels off
+  if (h->dr_enabled) ALLOC(h->d_mass_dr, 2 * sizeof(lm_mass_dr) + LM_DR_MASS_ROWS * N * sizeof(float));         // zeros: all three channels off
   ALLOC(h->d_obs, N * (size_t)h->num_obs * sizeof(float));
   ALLOC(h->d_states, N * 93 * sizeof(float));
   ALLOC(h->d_rew, N * sizeof(float));
@@ -2043,6 +2150,21 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
   if (hipMemcpy(h->d_params, h->h_params, 2 * sizeof(lm_params), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(h->d_table, itab, LM_ITAB_FLOATS * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
     lm_destroy(h); return fail(LM_EHIP, "lm_create: parameter / table upload failed");
+  }
+  h->h_body_mass[0] = itab[0];
+  for (int l = 0; l < 4; l++) {
+    const float* d = itab + HUB_FLOATS + l * LIMB_STRIDE; float* m = h->h_body_mass + 1 + 5 * l;
+    m[0] = d[T_I0]; m[1] = d[T_Q1]; m[2] = d[T_Q2]; m[3] = d[T_Q1 + 1]; m[4] = d[T_Q2 + 1];      // shell, link4, link3, link1, link2
+  }
+  if (h->d_mass_dr) {      // the record starts at the nominal values: a step rewrites only the rows of the channels that are on
+    float* tmp = new float[LM_DR_MASS_ROWS * N];
+    for (size_t e = 0; e < N; e++) {
+      tmp[e] = h->h_params[(int)e >= h->split ? 1 : 0].plate_mass; tmp[N + e] = 1.f;
+      for (int b = 0; b < LM_NUM_BODIES; b++) tmp[(size_t)(2 + b) * N + e] = h->h_body_mass[b];
+    }
+    hipError_t e1 = hipMemcpy(h->d_mass_dr + 2, tmp, LM_DR_MASS_ROWS * N * sizeof(float), hipMemcpyHostToDevice);
+    delete[] tmp;
+    if (e1 != hipSuccess) { lm_destroy(h); return fail(LM_EHIP, "lm_create: initial upload failed"); }
   }
   // identity quaternions so that an un-reset state is still valid; reset_buf = 1 (rl_task.py:111)
   {
@@ -2059,7 +2181,7 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
 
 int lm_destroy(lm_engine* h) {
   if (!h) return LM_OK;
-  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_reset_dr, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats};
+  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_reset_dr, h->d_mass_dr, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   delete h;
   return LM_OK;
@@ -2079,7 +2201,7 @@ static StepArgs make_args(lm_engine* h, const float* actions, const float* goal_
   A.W.obs_buf = h->d_obs; A.W.states_buf = h->d_states; A.W.rew_buf = h->d_rew; A.W.terms = h->d_terms; A.W.acc = h->d_acc;
   A.W.stats = (char*)h->d_stats; A.W.extras = h->d_extras; A.W.out_extras = nullptr; A.W.split_block = h->split / ENVS_PER_WAVE; A.W.acc_rows = h->acc_rows;
   A.W.out_obs = out_obs; A.W.out_states = out_states; A.W.out_rew = out_rew; A.W.out_resets = out_resets;
-  A.N = h->N; A.split = h->split; A.seed = h->seed; A.skip_reset = 0; A.nsub = -1; A.drc = h->d_drc; A.dr_phys = h->d_dr_phys; A.reset_dr = h->d_reset_dr;
+  A.N = h->N; A.split = h->split; A.seed = h->seed; A.skip_reset = 0; A.nsub = -1; A.drc = h->d_drc; A.dr_phys = h->d_dr_phys; A.reset_dr = h->d_reset_dr; A.mass_dr = h->d_mass_dr;
   for (int t = 0; t < 2; t++) A.kind[t] = h->h_params[t].variant * 2 + (h->h_params[t].mode == LM_MODE_MANI ? 1 : 0);
   return A;
 }
@@ -2152,6 +2274,44 @@ int lm_set_reset_randomization(lm_engine* h, int block, const lm_reset_dr* rd) {
   return LM_OK;
 }
 
+// least mass (or density factor) a bounded distribution can produce from `nominal`: <= 0 is refused
+static bool mass_range_ok(const lm_dr_channel& ch, float p0, float p1, float nominal) {
+  if (ch.distribution == LM_DR_GAUSSIAN) return true;      // unbounded: the floor takes the tail
+  const float lo = p0 < p1 ? p0 : p1;
+  const float least = ch.operation == LM_DR_ADDITIVE ? nominal + lo : ch.operation == LM_DR_SCALING ? nominal * lo : lo;
+  return least > 0.f;
+}
+int lm_set_mass_randomization(lm_engine* h, int block, const lm_mass_dr* md) {
+  if (!h || !md) return fail(LM_EINVAL, "lm_set_mass_randomization: null argument");
+  if (!h->dr_enabled || !h->d_mass_dr) return fail(LM_EINVAL, "lm_set_mass_randomization: the engine was created without dr_enabled");
+  if (block < 0 || block >= h->n_tasks) return fail(LM_EINVAL, "lm_set_mass_randomization: block must be 0 (or 1 on a two-task engine)");
+  CHECK_DEVICE(h, "lm_set_mass_randomization");
+  const lm_params& P = h->h_params[block];
+  float s_least = 1.f;      // least density factor: the nominal of the plate-mass channel is s x plate_mass
+  for (int c = 0; c < LM_DR_MASS_CHANNELS; c++) {
+    const lm_dr_channel& ch = md->ch[c == 0 ? LM_DR_MASS_PLATE_DENSITY : c == 1 ? LM_DR_MASS_PLATE : LM_DR_MASS_BODIES];      // density first
+    const int kind = (int)(&ch - md->ch);
+    if (!ch.enabled) continue;
+    if (ch.operation < 0 || ch.operation > 2 || ch.distribution < 0 || ch.distribution > 2 || ch.interval < LM_DR_ON_STARTUP)
+      return fail(LM_EINVAL, "lm_set_mass_randomization: invalid operation / distribution / interval");
+    if (kind != LM_DR_MASS_BODIES && P.mode != LM_MODE_MANI)
+      return fail(LM_EINVAL, "lm_set_mass_randomization: the plate channels exist on manipulation blocks only");
+    if (kind == LM_DR_MASS_PLATE_DENSITY && (ch.interval != LM_DR_ON_STARTUP || ch.operation != LM_DR_SCALING))
+      return fail(LM_EINVAL, "lm_set_mass_randomization: the density channel is on_startup + scaling only (no nominal density exists: the URDF gives mass and inertia, no volume)");
+    const int n = kind == LM_DR_MASS_BODIES ? LM_NUM_BODIES : 1;
+    for (int k = 0; k < n; k++) {
+      const float p0 = kind == LM_DR_MASS_BODIES ? md->body_p0[k] : ch.p0[0], p1 = kind == LM_DR_MASS_BODIES ? md->body_p1[k] : ch.p1[0];
+      if (!std::isfinite(p0) || !std::isfinite(p1)) return fail(LM_EINVAL, "lm_set_mass_randomization: non-finite distribution parameters");
+      if (ch.distribution == LM_DR_LOGUNIFORM && !(p0 > 0 && p1 > 0)) return fail(LM_EINVAL, "lm_set_mass_randomization: log-uniform bounds must be positive");
+      const float nominal = kind == LM_DR_MASS_BODIES ? h->h_body_mass[k] : kind == LM_DR_MASS_PLATE ? s_least * P.plate_mass : 1.f;
+      if (!mass_range_ok(ch, p0, p1, nominal)) return fail(LM_EINVAL, "lm_set_mass_randomization: the distribution's range reaches a non-positive mass");
+      if (kind == LM_DR_MASS_PLATE_DENSITY) s_least = ch.distribution == LM_DR_GAUSSIAN ? LM_DR_MASS_FLOOR : (p0 < p1 ? p0 : p1);
+    }
+  }
+  HIPCHK(hipMemcpy(h->d_mass_dr + block, md, sizeof(lm_mass_dr), hipMemcpyHostToDevice));
+  return LM_OK;
+}
+
 int lm_reset_all(lm_engine* h, void* stream) {
   if (!h) return fail(LM_EINVAL, "lm_reset_all: null handle");
   CHECK_DEVICE(h, "lm_reset_all");
@@ -2218,6 +2378,7 @@ void* lm_ptr(lm_engine* h, int kind) {
     case LM_PTR_DR_CNT: return h->d_drc;
     case LM_PTR_DR_PHYS: return h->d_dr_phys;
     case LM_PTR_DR_RESET_STATE: return h->d_reset_dr ? (void*)(h->d_reset_dr + 2) : nullptr;
+    case LM_PTR_DR_MASS: return h->d_mass_dr ? (void*)(h->d_mass_dr + 2) : nullptr;
     case LM_PTR_OBS_BUF: h->view_obs = true; return h->d_obs;
     case LM_PTR_STATES_BUF: h->view_states = true; return h->d_states;
     case LM_PTR_REW_BUF: return h->d_rew;

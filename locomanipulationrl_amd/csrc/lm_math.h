@@ -97,8 +97,8 @@ template <class T> LM_DEV SIT<T> operator+(const SIT<T>& a, const SIT<T>& b) {
 LM_DEV SI lo(const SIP& a) { SI r; r.m = a.m.x; r.h = lo(a.h); r.xx = a.xx.x; r.yy = a.yy.x; r.zz = a.zz.x; r.xy = a.xy.x; r.xz = a.xz.x; r.yz = a.yz.x; return r; }
 LM_DEV SI hi(const SIP& a) { SI r; r.m = a.m.y; r.h = hi(a.h); r.xx = a.xx.y; r.yy = a.yy.y; r.zz = a.zz.y; r.xy = a.xy.y; r.xz = a.xz.y; r.yz = a.yz.y; return r; }
 // body inertia (m, com in body frame, I about COM in body axes [xx,yy,zz,xy,xz,yz]) placed at pose (R,o) -> about O
-template <class T> LM_DEV SIT<T> place_inertia(const T* t, const M3T<T>& R, V3T<T> o) {
-  T m = t[0];
+// (place_inertia_m: the mass given by the caller instead of t[0] - the per-env masses of the randomised kernels; COM and I about COM stay t's)
+template <class T> LM_DEV SIT<T> place_inertia_m(const T* t, T m, const M3T<T>& R, V3T<T> o) {
   V3T<T> c = o + mul(R, v3t<T>(t[1], t[2], t[3]));
   // T = R * Ib (Ib symmetric), Iw = T * R^T
   V3T<T> t0 = fma3(t[4], R.c0, fma3(t[7], R.c1, t[8] * R.c2));   // T col0 = R * Ib col0 = xx*c0 + xy*c1 + xz*c2
@@ -115,6 +115,7 @@ template <class T> LM_DEV SIT<T> place_inertia(const T* t, const M3T<T>& R, V3T<
   I.yz = t0.y * R.c0.z + t1.y * R.c1.z + t2.y * R.c2.z - m * c.y * c.z;
   return I;
 }
+template <class T> LM_DEV SIT<T> place_inertia(const T* t, const M3T<T>& R, V3T<T> o) { return place_inertia_m<T>(t, t[0], R, o); }
 
 // ---- 4-lane (one env) cross-lane helpers: DPP quad permutes, no LDS traffic
 LM_DEV float quad_xor1(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)); }

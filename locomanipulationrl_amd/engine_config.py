@@ -72,6 +72,14 @@ DR_RESET_JOINT_POS, DR_RESET_JOINT_VEL, DR_RESET_POSITION, DR_RESET_ORIENTATION 
 DR_RESET_CHANNELS = 4
 DR_RESET_ROWS = 31                  # rows of Engine.dr_reset_state: q 12, qd 12, free-body position 3, quaternion (w, x, y, z) 4
 DR_STREAM_RESET = 12                # random streams 12..15, after the material streams 10, 11
+# mass channels (include/lm_engine.h LM_DR_MASS_*): per-env masses of the plate and of the robot's 21 bodies, drawn in the step launch.
+# Kept out of `dr` as well: they reach the engine through lm_set_mass_randomization.  interval as for the material channels (DR_ON_STARTUP / 0 / >= 1)
+DR_MASS_PLATE, DR_MASS_PLATE_DENSITY, DR_MASS_BODIES = range(3)
+DR_MASS_CHANNELS = 3
+NUM_BODIES = 21
+DR_MASS_ROWS = 23                   # rows of Engine.dr_mass: plate mass, plate inertia factor, 21 body masses in table order
+DR_MASS_FLOOR = 0.05                # a drawn mass is floored at this fraction of its nominal (LM_DR_MASS_FLOOR)
+DR_STREAM_MASS = 16                 # random streams 16 (plate mass), 17 (plate density), 18 (body masses)
 FRICTION_COMBINE = {"average": 0, "min": 1, "multiply": 2, "max": 3}      # PhysX's PxCombineMode order (LM_COMBINE_*)
 
 
@@ -103,6 +111,10 @@ def _no_mat():
 
 def _no_reset():
     return [DRChannel() for _ in range(DR_RESET_CHANNELS)]
+
+
+def _no_mass():
+    return [DRChannel() for _ in range(DR_MASS_CHANNELS)]
 
 
 @dataclass
@@ -202,6 +214,14 @@ class EngineParams:
     # gate the env starts from operation(nominal, draw) instead of init_q / zero joint velocity / the free body's init pose (the base in
     # locomotion blocks, the plate in manipulation blocks).  on_reset only (interval 0); not part of the C parameter block
     dr_reset: List[DRChannel] = field(default_factory=_no_reset)
+    # mass channels [plate mass, plate density, body masses]: operation(nominal, draw) per env, floored at DR_MASS_FLOOR x nominal.
+    # `mass` channels change the mass only (COM and inertia about the COM stay); the density channel is a factor on the plate's mass and inertia
+    # (on_startup + scaling only), applied first.  The two plate channels read p0[0] / p1[0]; the body channel reads dr_mass_body_p0 / _p1, one pair
+    # per body in TABLE order (RobotModel.table_body_order(): hub, then per limb shell, link4, link3, link1, link2).  Plate channels: manipulation
+    # blocks only.  Not part of the C parameter block
+    dr_mass: List[DRChannel] = field(default_factory=_no_mass)
+    dr_mass_body_p0: List[float] = _f([0.0] * NUM_BODIES)
+    dr_mass_body_p1: List[float] = _f([0.0] * NUM_BODIES)
     # ---- RobotOmni.take_action control mode (robot/base/robot.py:444-461), variant 0 only: 0 velocity (every task of the path), 1 position
     # (target a * act_scale rad with act_scale = pi, PD gains pd_kp / kd), 2 effort (torque a * act_scale N m with act_scale = torque limit)
     drive_mode: int = 0

@@ -19,10 +19,11 @@ _SO = os.environ.get("LM_ENGINE_SO", os.path.join(_CSRC, "liblm_engine.so"))    
 STATE_ROWS, CNT_ROWS, NUM_OBS, NUM_STATES, NUM_ACTIONS, NUM_EXTRAS, TABLE_FLOATS, TERM_ROWS, READBACK = 115, 6, 64, 93, 12, 13, 502, 11, 99
 DR_PHYS_ROWS, DR_PHYS_MU = 43, 42       # LM_DR_PHYS_ROWS, LM_DR_PHYS_MU
 DR_RESET_CHANNELS, DR_RESET_ROWS = 4, 31      # LM_DR_RESET_CHANNELS, LM_DR_RESET_ROWS
-PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE = range(11)
+DR_MASS_CHANNELS, DR_MASS_ROWS, NUM_BODIES = 3, 23, 21      # LM_DR_MASS_CHANNELS, LM_DR_MASS_ROWS, LM_NUM_BODIES
+PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS = range(12)
 
 # names of the exported C symbols (checked by tests/test_abi.py against include/lm_engine.h)
-EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
+EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass_randomization", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
            "lm_forward_kinematics", "lm_debug_dynamics", "lm_ptr", "lm_num_envs", "lm_num_obs", "lm_set_seed", "lm_last_error", "lm_version", "lm_abi_version",
            "lm_gnn_param_count", "lm_gnn_forward", "lm_mlp_param_count", "lm_mlp_forward", "lm_mlp_param_count_obs", "lm_mlp_forward_obs",
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy"]
@@ -54,6 +55,26 @@ def make_reset_dr(ep) -> LmResetDr:
     r = LmResetDr()
     for i, ch in enumerate(getattr(ep, "dr_reset", None) or []):
         _fill_channel(r.ch[i], ch)
+    return r
+
+
+class LmMassDr(C.Structure):
+    """lm_mass_dr: the three mass channels of one parameter block (plate mass, plate density, body masses) and the per-body parameters of
+    the last one, in table order."""
+    _fields_ = [("ch", LmDrChannel * DR_MASS_CHANNELS), ("body_p0", C.c_float * NUM_BODIES), ("body_p1", C.c_float * NUM_BODIES)]
+
+
+def make_mass_dr(ep) -> LmMassDr:
+    """EngineParams.dr_mass / dr_mass_body_p0 / dr_mass_body_p1 -> C struct (all channels off for a block that carries none)."""
+    r = LmMassDr()
+    for i, ch in enumerate(getattr(ep, "dr_mass", None) or []):
+        _fill_channel(r.ch[i], ch)
+    for dst, name in ((r.body_p0, "dr_mass_body_p0"), (r.body_p1, "dr_mass_body_p1")):
+        vals = list(getattr(ep, name, None) or [])
+        if vals and len(vals) != NUM_BODIES:
+            raise ValueError(f"EngineParams.{name}: {NUM_BODIES} values (table order) are needed, got {len(vals)}")
+        for k, x in enumerate(vals):
+            dst[k] = float(x)
     return r
 
 
@@ -183,6 +204,7 @@ def load_library() -> C.CDLL:
     lib.lm_create.argtypes = [C.POINTER(vp), ip, C.c_void_p, C.POINTER(LmParams), ip, ip, C.c_uint32]
     lib.lm_destroy.argtypes = [vp]
     lib.lm_set_reset_randomization.argtypes = [vp, ip, C.POINTER(LmResetDr)]
+    lib.lm_set_mass_randomization.argtypes = [vp, ip, C.POINTER(LmMassDr)]
     lib.lm_step.argtypes = [vp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.lm_post_physics.argtypes = [vp, fp, fp, fp, fp, fp, fp, vp]
     lib.lm_reset_all.argtypes = [vp, vp]
@@ -251,6 +273,10 @@ class Engine:
                 rd = make_reset_dr(ep)
                 with torch.cuda.device(self.device):
                     self._check(self.lib.lm_set_reset_randomization(self._h, b, C.byref(rd)))
+            if any(ch.enabled for ch in (getattr(ep, "dr_mass", None) or [])):          # mass channels: the same way
+                md = make_mass_dr(ep)
+                with torch.cuda.device(self.device):
+                    self._check(self.lib.lm_set_mass_randomization(self._h, b, C.byref(md)))
         self.seed = int(seed) & 0xFFFFFFFF
         N = self.num_envs
         self.state = self._wrap(PTR_STATE, (STATE_ROWS, N), "<f4")
@@ -301,6 +327,28 @@ class Engine:
                 raise EngineError("dr_reset_state: the engine was created without dr_enabled (no reset-state record)")
             self._views["dr_reset_state"] = self.torch.as_tensor(_DevArray(ptr, (DR_RESET_ROWS, self.num_envs), "<f4", self), device=self.device)
         return self._views["dr_reset_state"]
+
+    @property
+    def dr_mass(self):
+        """float [23][N]: the masses the last step used, floored - row 0 the plate's mass, row 1 the factor on its inertia about the COM,
+        rows 2..22 the 21 body masses in table order (RobotModel.table_body_order()).  The nominal values until a mass channel draws.
+        Randomised engines only (dr_enabled)."""
+        if "dr_mass" not in self._views:
+            ptr = self.lib.lm_ptr(self._h, PTR_DR_MASS)
+            if not ptr:
+                raise EngineError("dr_mass: the engine was created without dr_enabled (no mass record)")
+            self._views["dr_mass"] = self.torch.as_tensor(_DevArray(ptr, (DR_MASS_ROWS, self.num_envs), "<f4", self), device=self.device)
+        return self._views["dr_mass"]
+
+    @property
+    def dr_plate_mass(self):
+        """float [N]: row 0 of dr_mass."""
+        return self.dr_mass[0]
+
+    @property
+    def dr_body_masses(self):
+        """float [21][N]: rows 2..22 of dr_mass (table order)."""
+        return self.dr_mass[2:]
 
     @property
     def blowups(self) -> int:

@@ -142,6 +142,11 @@ class RobotModel:
         poses = self.fk(q12, base_R, base_p)
         return np.stack([poses[b][1] for b in self.knee_body])
 
+    def table_body_order(self) -> List[int]:
+        """Generic body index (into `mass`, `body_names` ...) of each slot of the engine's table order: the hub, then per limb
+        shell, link4, link3, link1, link2 (LIMB_BODIES).  The per-body parameters and records of the mass channels use this order."""
+        return [0] + [int(k) for k in np.asarray(self.limb_body_index).ravel()]
+
     # ------------------------------------------------------------------ packed kernel table
     def packed_table(self) -> np.ndarray:
         """float32 table: hub (m, com3, I6 about COM [xx,yy,zz,xy,xz,yz]) then 4 limbs of LIMB_STRIDE.

@@ -158,7 +158,10 @@ class _QuadrupedTask(RLTask):
         if any(ch.enabled for ch in base.get("dr_mat", [])) and base["friction_combine"] < 0:
             raise ValueError(f"sim.engine.friction_combine {comb!r}: one of {sorted(FRICTION_COMBINE)} is needed with material_properties randomisation")
         base.update(kw)
-        return EngineParams(**base)
+        ep = EngineParams(**base)
+        if ep.mode == MODE_MANI:
+            self._dr_randomizer.check_plate_mass_range(ep.plate_mass)          # a plate-mass entry must keep THIS block's plate positive
+        return ep
 
     def _loco_params(self, robot) -> EngineParams:
         rd = robot.robot_description

@@ -31,8 +31,18 @@ Supported entries (everything the reference's YAMLs enable):
     rigid_prim_views.plate.position / .orientation     the same for the plate of the manipulation blocks (the robot is fixed there)
                                                        (EngineParams.dr_reset; DESIGN.md 3.6: drawn inside the step launch at every reset that
                                                        passes min_frequency; no clamping to the joint ranges)
-Anything else (mass, density, material_properties of other views, stiffness ...) raises NotImplementedError when
-`randomize: True` - a silently ignored randomisation would be worse than a loud one."""
+    rigid_prim_views.plate.mass                        on_startup | on_reset | on_interval, additive | scaling | direct, [a, b]: the plate's mass per
+                                                       env (manipulation blocks).  Mass only: COM and inertia about the COM stay
+    rigid_prim_views.plate.density                     on_startup, scaling only: a factor on the plate's mass AND inertia, applied before `mass`
+                                                       (the URDF gives no volume, so there is no nominal density to add to or to replace)
+    articulation_views.<robot>.body_masses             on_startup | on_reset | on_interval, additive | scaling | direct: the masses of the 21 bodies,
+                                                       one draw per body; [a, b] for all bodies or [[21 values], [21 values]] in
+                                                       RobotModel.body_names order.  Mass only.  Component 0 is the base link: a payload
+                                                       (EngineParams.dr_mass; DESIGN.md 3.6: drawn inside the step launch, floored at 0.05 x nominal;
+                                                       a uniform / loguniform range that reaches a non-positive mass is refused; parity with the
+                                                       replicator is unpinned, as for every physics attribute)
+Anything else (mass / density of other rigid-prim views - the base link's included: use body_masses -, body_inertias, material_properties of
+other views, stiffness ...) raises NotImplementedError when `randomize: True` - a silently ignored randomisation would be worse than a loud one."""
 from __future__ import annotations
 
 from typing import List
@@ -40,8 +50,8 @@ from typing import List
 import numpy as np
 
 from ...engine_config import (DR_ACT_INTERVAL, DR_ACT_RESET, DR_BASE_FORCE, DR_CHANNELS, DR_DISTRIBUTIONS, DR_GRAVITY, DR_JOINT_DAMPING, DR_MAT_OTHER,
-                              DR_MAT_ROBOT, DR_MAX_EFFORT, DR_MAX_VELOCITY, DR_OBS_INTERVAL, DR_OBS_RESET, DR_ON_STARTUP, DR_OPERATIONS, DR_RESET_CHANNELS,
-                              DR_RESET_JOINT_POS, DR_RESET_JOINT_VEL, DR_RESET_ORIENTATION, DR_RESET_POSITION, MODE_LOCO, MODE_MANI, DRChannel)
+                              DR_MAT_ROBOT, DR_MASS_BODIES, DR_MASS_CHANNELS, DR_MASS_FLOOR, DR_MASS_PLATE, DR_MASS_PLATE_DENSITY, DR_MAX_EFFORT, DR_MAX_VELOCITY, DR_OBS_INTERVAL, DR_OBS_RESET, DR_ON_STARTUP, DR_OPERATIONS, DR_RESET_CHANNELS,
+                              DR_RESET_JOINT_POS, DR_RESET_JOINT_VEL, DR_RESET_ORIENTATION, DR_RESET_POSITION, MODE_LOCO, MODE_MANI, NUM_BODIES, DRChannel)
 
 _ON_RESET_KEYS = ("operation", "distribution", "distribution_parameters")
 _ON_INTERVAL_KEYS = ("frequency_interval", "operation", "distribution", "distribution_parameters")
@@ -156,6 +166,66 @@ def _reset_state_channel(where: str, attribute: str, entry: dict) -> DRChannel:
     return ch
 
 
+_MASS_REFUSED = ("rigid_prim_views.{view}.{attribute}: only the plate's mass / density are channels of this engine (rigid_prim_views." + PLATE_VIEW +
+                 ".mass / .density); the masses of the robot's links - the base link's included, e.g. a payload - are "
+                 "articulation_views.<robot>.body_masses, whose component 0 is the base link")
+_NO_PLATE = ("rigid_prim_views.{view}.{attribute}: this task has no manipulation block, so there is no plate whose {attribute} could be randomised; "
+             "the robot's masses are articulation_views.<robot>.body_masses")
+
+
+def _mass_channel(where: str, attribute: str, entry: dict):
+    """One mass entry (plate `mass` / `density`, `body_masses`) -> (trigger, DRChannel, per-body low / mean, per-body high / std or None)."""
+    if entry is None:
+        raise ValueError(f"Randomization parameters for {where} is not provided.")
+    triggers = [t for t in ("on_startup", "on_reset", "on_interval") if t in entry]
+    if len(triggers) != 1:
+        raise NotImplementedError(f"{where}: give exactly one of on_startup, on_reset, on_interval")
+    trigger = triggers[0]
+    e = entry[trigger]
+    need = _ON_INTERVAL_KEYS if trigger == "on_interval" else _ON_RESET_KEYS
+    if e is None or not set(need).issubset(e.keys()):
+        raise ValueError(f"Please ensure the following randomization parameters for {where} {trigger} are provided: " + ", ".join(need) + ".")
+    op, dist = str(e["operation"]), str(e["distribution"])
+    if op not in DR_OPERATIONS or dist not in DR_DISTRIBUTIONS:
+        raise ValueError(f"{where} {trigger}: unsupported operation {op!r} or distribution {dist!r}")
+    if attribute == "density":
+        why = "the URDF gives the plate's mass and inertia but no volume, so no nominal density exists"
+        if trigger != "on_startup":
+            raise NotImplementedError(f"{where} {trigger}: density is an on_startup entry (a factor on the plate's mass and inertia, drawn once per env); {why}")
+        if op != "scaling":
+            raise ValueError(f"{where} {trigger}: operation {op!r} is refused: {why} - only a scaling factor is defined")
+    raw = e["distribution_parameters"]
+    try:
+        prm = np.asarray(raw, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{where} {trigger}: distribution_parameters must be numbers, got {raw!r}") from None
+    per_body = attribute == "body_masses" and prm.ndim == 2
+    if not (prm.shape == (2,) or (per_body and prm.shape == (2, NUM_BODIES))):
+        raise ValueError(f"{where} {trigger}: distribution_parameters must be [a, b]" +
+                         (f" or [[{NUM_BODIES} values], [{NUM_BODIES} values]] in RobotModel.body_names order" if attribute == "body_masses" else "") + f", got shape {prm.shape}")
+    if not np.isfinite(prm).all():
+        raise ValueError(f"{where} {trigger}: distribution_parameters must be finite")
+    if DR_DISTRIBUTIONS[dist] == DR_DISTRIBUTIONS["loguniform"] and not (prm > 0).all():
+        raise ValueError(f"{where} {trigger}: loguniform parameters must be positive")
+    interval = {"on_startup": DR_ON_STARTUP, "on_reset": 0}.get(trigger)
+    if interval is None:
+        interval = int(e["frequency_interval"])
+        if interval < 1:
+            raise ValueError(f"{where}: frequency_interval must be >= 1")
+    lo, hi = (prm[0], prm[1]) if per_body else (np.full(NUM_BODIES, prm[0]), np.full(NUM_BODIES, prm[1]))
+    ch = DRChannel(enabled=1, operation=DR_OPERATIONS[op], distribution=DR_DISTRIBUTIONS[dist], interval=interval,
+                   p0=[float(lo[0])] * 3, p1=[float(hi[0])] * 3)
+    return trigger, ch, lo.astype(np.float64), hi.astype(np.float64)
+
+
+def _least_mass(ch: DRChannel, lo: float, hi: float, nominal: float):
+    """The least value a bounded distribution (uniform, loguniform) can give a mass of `nominal`; None for the unbounded gaussian (floored)."""
+    if ch.distribution == DR_DISTRIBUTIONS["gaussian"]:
+        return None
+    low = min(lo, hi)
+    return nominal + low if ch.operation == DR_OPERATIONS["additive"] else nominal * low if ch.operation == DR_OPERATIONS["scaling"] else low
+
+
 class Randomizer:
     def __init__(self, sim_config):
         self._cfg = sim_config.task_config
@@ -169,6 +239,11 @@ class Randomizer:
         # reset-state channels per block mode (EngineParams.dr_reset): the joint entries go to both, position / orientation to the block
         # whose free body they name (articulation_views.<robot>: the base of locomotion blocks; rigid_prim_views.plate: manipulation blocks)
         self._reset_channels = {MODE_LOCO: [DRChannel() for _ in range(DR_RESET_CHANNELS)], MODE_MANI: [DRChannel() for _ in range(DR_RESET_CHANNELS)]}
+        # mass channels (EngineParams.dr_mass): [plate mass, plate density, body masses]; the plate's go to manipulation blocks only.  The body
+        # channel's parameters per body, in table order
+        self._mass_channels: List[DRChannel] = [DRChannel() for _ in range(DR_MASS_CHANNELS)]
+        self._mass_body_p0: List[float] = [0.0] * NUM_BODIES
+        self._mass_body_p1: List[float] = [0.0] * NUM_BODIES
         self._observations_dr_params = None
         self._actions_dr_params = None
         self.startup_scales = dict()          # (group, view) -> per-env factors drawn by apply_on_startup_domain_randomization
@@ -190,7 +265,8 @@ class Randomizer:
         simulates are unchanged.  Here the entry is therefore ACCEPTED: the per-env factors are drawn as the reference draws them (one
         synchronised factor per env, torch generator seeded with the config seed, randomize.py:60,308-350) and kept in `startup_scales`
         for inspection, a warning says that they do not enter the dynamics, and the compiled model table stays shared by all envs.
-        mass / density on_startup entries would change that table per env and are refused.
+        The plate's mass / density and the robot's body_masses are channels of the engine (set_up_domain_randomization); mass / density of any
+        other rigid-prim view are refused here.
         PARITY UNPINNED: whether PhysX rescales anything on `set_local_scales` rests on that question-marked author comment (the same line
         sits in every task YAML of the reference, e.g. JointLocomanipulation.yaml:166), and the factors come from a private torch.Generator
         seeded with the config seed, not from the global stream the reference seeds with `torch.manual_seed` before
@@ -209,6 +285,14 @@ class Randomizer:
                         continue          # material_properties on_startup is a channel of the engine (set_up_domain_randomization)
                     if attribute in _RESET_STATE:
                         continue          # reset-state entries: set_up_domain_randomization refuses every trigger but on_reset, with the reason
+                    if attribute == "body_masses" and group == "articulation_views":
+                        continue          # a mass channel of the engine (set_up_domain_randomization)
+                    if attribute in ("mass", "density") and group == "rigid_prim_views":
+                        if view != PLATE_VIEW:
+                            raise NotImplementedError(_MASS_REFUSED.format(view=view, attribute=attribute))
+                        if not hasattr(task, "robot_manipulation"):
+                            raise NotImplementedError(_NO_PLATE.format(view=view, attribute=attribute))
+                        continue          # the plate's mass / density: mass channels of the engine too
                     st = entry["on_startup"]
                     if not set(_ON_RESET_KEYS).issubset(st.keys()):          # randomize.py:75-77,104-106
                         raise ValueError(f"Please ensure the following randomization parameters for {view} {attribute} on_startup are provided: "
@@ -216,8 +300,7 @@ class Randomizer:
                     if attribute == "scale" and bool((self._cfg.get("sim", {}).get("engine", {}) or {}).get("refuse_startup_scale", False)):
                         raise NotImplementedError(f"{group}.{view}.scale on_startup does not enter this engine's dynamics (sim.engine.refuse_startup_scale is set)")
                     if attribute != "scale":
-                        raise NotImplementedError(f"domain randomisation of {group}.{view}.{attribute} on_startup is not implemented "
-                                                  "(mass / density change the compiled model table per env)")
+                        raise NotImplementedError(f"domain randomisation of {group}.{view}.{attribute} on_startup is not implemented")
                     n = int(self._cfg["env"]["numEnvs"])
                     g = torch.Generator().manual_seed(int(self._config.get("seed", 42)))
                     lo, hi = (float(x) for x in st["distribution_parameters"])
@@ -261,8 +344,15 @@ class Randomizer:
             elif opt == "rigid_prim_views":
                 for view, attrs in (body or {}).items():
                     for attribute, entry in (attrs or {}).items():
-                        if attribute in ("scale", "mass", "density"):
-                            continue          # on_startup entries, handled (refused) above
+                        if attribute == "scale":
+                            continue          # on_startup entry, handled above
+                        if attribute in ("mass", "density"):
+                            if view != PLATE_VIEW:
+                                raise NotImplementedError(_MASS_REFUSED.format(view=view, attribute=attribute))
+                            if not hasattr(task, "robot_manipulation"):
+                                raise NotImplementedError(_NO_PLATE.format(view=view, attribute=attribute))
+                            self._set_up_mass(("rigid_prim_views", view, attribute), entry, DR_MASS_PLATE if attribute == "mass" else DR_MASS_PLATE_DENSITY, task)
+                            continue
                         if attribute == "material_properties" and view == PLATE_VIEW:
                             self._set_up_material(("rigid_prim_views", view, attribute), entry, DR_MAT_OTHER)
                             continue
@@ -282,6 +372,9 @@ class Randomizer:
                             continue
                         if attribute == "material_properties":          # the feet: the robot's only colliders
                             self._set_up_material(("articulation_views", view, attribute), entry, DR_MAT_ROBOT)
+                            continue
+                        if attribute == "body_masses":
+                            self._set_up_mass(("articulation_views", view, attribute), entry, DR_MASS_BODIES, task)
                             continue
                         if attribute == "joint_friction":          # the joint friction coefficient itself is not modelled: scaling it changes nothing
                             import warnings
@@ -303,6 +396,7 @@ class Randomizer:
                         self._set_up_attribute(("articulation_views", view, attribute), entry, ch, vector=False)
             else:
                 raise ValueError(f"unknown domain randomisation group {opt!r}")
+        self._check_mass_ranges(task)
 
     def _set_up_noise(self, task, kind, body, ch_reset, ch_interval):
         if body is None:
@@ -335,6 +429,52 @@ class Randomizer:
             self._reset_channels[m][_RESET_STATE[attribute][0]] = ch
         self.active_domain_randomizations[key + ("on_reset",)] = np.array(entry["on_reset"]["distribution_parameters"])
 
+    def _set_up_mass(self, key, entry, ch, task):
+        """plate mass / density or body_masses: one trigger -> the mass channel `ch`; per-body parameters go from body_names order to table order."""
+        trigger, c, lo, hi = _mass_channel(".".join(key), key[-1], entry)
+        self._mass_channels[ch] = c
+        if ch == DR_MASS_BODIES:
+            order = self._robot_model(task).table_body_order()
+            self._mass_body_p0 = [float(lo[k]) for k in order]
+            self._mass_body_p1 = [float(hi[k]) for k in order]
+        self.active_domain_randomizations[key + (trigger,)] = np.array(entry[trigger]["distribution_parameters"])
+
+    @staticmethod
+    def _robot_model(task):
+        from ...model.robot_model import load_model
+        return load_model(getattr(task, "model_asset", "quadruped_robot_v2"))
+
+    def _check_mass_ranges(self, task):
+        """A bounded distribution whose range reaches a non-positive mass is refused (the floor is for gaussian tails only).  The density factor
+        and the body masses are checked here; the plate's mass against the plate of the block it reaches (check_plate_mass_range)."""
+        cd, cb = self._mass_channels[DR_MASS_PLATE_DENSITY], self._mass_channels[DR_MASS_BODIES]
+        if cd.enabled:
+            least = _least_mass(cd, cd.p0[0], cd.p1[0], 1.0)
+            if least is not None and least <= 0:
+                raise ValueError(f"rigid_prim_views.{PLATE_VIEW}.density: the distribution's range reaches a non-positive factor ({least:g})")
+        if cb.enabled:
+            rm = self._robot_model(task)
+            for slot, k in enumerate(rm.table_body_order()):
+                least = _least_mass(cb, self._mass_body_p0[slot], self._mass_body_p1[slot], float(rm.mass[k]))
+                if least is not None and least <= 0:
+                    raise ValueError(f"articulation_views.<robot>.body_masses: the distribution's range reaches a non-positive mass ({least:g} kg) for "
+                                     f"body {rm.body_names[k]!r}; a gaussian is floored instead, a uniform / loguniform range must stay positive")
+
+    def check_plate_mass_range(self, plate_mass: float):
+        """The plate-mass entry against the nominal of the manipulation block it reaches: `plate_mass` of that block times the least density
+        factor.  Called by the task when it builds the block, so a task with another plate is checked against its own."""
+        cp, cd = self._mass_channels[DR_MASS_PLATE], self._mass_channels[DR_MASS_PLATE_DENSITY]
+        if not (self.randomize and cp.enabled):
+            return
+        s_least = 1.0
+        if cd.enabled:
+            least = _least_mass(cd, cd.p0[0], cd.p1[0], 1.0)
+            s_least = DR_MASS_FLOOR if least is None else least
+        least = _least_mass(cp, cp.p0[0], cp.p1[0], s_least * float(plate_mass))
+        if least is not None and least <= 0:
+            raise ValueError(f"rigid_prim_views.{PLATE_VIEW}.mass: the distribution's range reaches a non-positive mass ({least:g} kg on a plate of "
+                             f"{s_least * float(plate_mass):g} kg); a gaussian is floored instead, a uniform / loguniform range must stay positive")
+
     def _set_up_material(self, key, entry, ch):
         """material_properties of the robot (ch = DR_MAT_ROBOT) or the plate (DR_MAT_OTHER): one trigger, dynamic component into the engine."""
         where = ".".join(key)
@@ -364,8 +504,12 @@ class Randomizer:
         mat = list(self._mat_channels); buckets = list(self._mat_buckets)
         if mode != MODE_MANI:
             mat[DR_MAT_OTHER] = DRChannel(); buckets[DR_MAT_OTHER] = 0
+        mass = list(self._mass_channels)
+        if mode != MODE_MANI:          # the plate's mass / density: manipulation blocks only
+            mass[DR_MASS_PLATE] = DRChannel(); mass[DR_MASS_PLATE_DENSITY] = DRChannel()
         return dict(dr_enabled=1, dr_min_frequency=int(self.min_frequency), dr=list(self._channels), dr_mat=mat, dr_mat_buckets=buckets,
-                    dr_reset=list(self._reset_channels[MODE_MANI if mode == MODE_MANI else MODE_LOCO]))
+                    dr_reset=list(self._reset_channels[MODE_MANI if mode == MODE_MANI else MODE_LOCO]),
+                    dr_mass=mass, dr_mass_body_p0=list(self._mass_body_p0), dr_mass_body_p1=list(self._mass_body_p1))
 
     # The wrapper calls these two exactly where the reference does (vec_env_rlgames.py:56-58,70-72).  The noise has already been /
     # will be applied inside lm_step with the reference's counter semantics (randomize.py:212-306), so they hand the tensor through.

@@ -1,7 +1,9 @@
 """Cost of domain randomisation inside the step launch: k_step vs k_step_dr (YAML block of QuadrupedPoseControl.yaml) at 4096 envs, and what
 the contact-material channel adds to k_step_dr (the same block + the feet's material_properties, redrawn every step in 64 buckets), and what
 the four reset-state channels add (the same block + joint_positions / joint_velocities / position / orientation at the reference's amplitudes,
-min_frequency 0: every reset draws; and behind the YAML's min_frequency, which outlasts the run: no reset draws).  `resets_per_step` is the mean number of envs reset per timed step of each leg."""
+min_frequency 0: every reset draws; and behind the YAML's min_frequency, which outlasts the run: no reset draws), and what the mass channels add
+(the same block + body_masses drawn once per env / redrawn every step; on QuadrupedManipulatePlate the same pair for the plate's mass, against that
+task's own randomised leg).  `resets_per_step` is the mean number of envs reset per timed step of each leg."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,14 +15,24 @@ MATERIAL = {"articulation_views": {"robot_view": {"material_properties": {"on_in
 _R = lambda prm: {"on_reset": dict(operation="additive", distribution="uniform", distribution_parameters=prm)}
 RESET_STATE = {"articulation_views": {"robot_view": {"joint_positions": _R([-0.1, 0.1]), "joint_velocities": _R([-0.1, 0.1]),
                                                      "position": _R([[-0.05, -0.05, 0.0], [0.05, 0.05, 0.1]]), "orientation": _R([[-0.1, -0.1, -1.2], [0.1, 0.1, 1.2]])}}}
+_M = lambda trigger, **kw: {trigger: dict(operation="scaling", distribution="uniform", distribution_parameters=[0.5, 2.0], **kw)}
+BODY_MASSES = lambda e: {"articulation_views": {"robot_view": {"body_masses": e}}}
+PLATE_MASS = lambda e: {"rigid_prim_views": {"plate": {"mass": e}}}
+_DR = lambda prm=None, **kw: {"task": {"domain_randomization": dict(randomize=True, **({"randomization_params": prm} if prm else {}), **kw)}}
+MANI = "QuadrupedManipulatePlate"
 resets = {}
 for name, ov in (("plain", None), ("randomised", {"task": {"domain_randomization": {"randomize": True}}}),
                  ("randomised_material", {"task": {"domain_randomization": {"randomize": True, "randomization_params": MATERIAL}}}),
                  ("randomised_min_frequency_0", {"task": {"domain_randomization": {"randomize": True, "min_frequency": 0}}}),
                  ("randomised_reset_state", {"task": {"domain_randomization": {"randomize": True, "min_frequency": 0, "randomization_params": RESET_STATE}}}),
                  # the same channels behind a gate that never opens (the YAML's min_frequency outlasts the run): what they cost the steps that do not draw
-                 ("randomised_reset_state_gate_closed", {"task": {"domain_randomization": {"randomize": True, "randomization_params": RESET_STATE}}})):
-    env = lm.make_env("QuadrupedPoseControl", num_envs=4096, overrides=ov)
+                 ("randomised_reset_state_gate_closed", {"task": {"domain_randomization": {"randomize": True, "randomization_params": RESET_STATE}}}),
+                 # mass channels: 21 draws per env once (on_startup: the hash runs every step, the key never changes) / redrawn every step
+                 ("randomised_body_masses_startup", _DR(BODY_MASSES(_M("on_startup")))),
+                 ("randomised_body_masses_every_step", _DR(BODY_MASSES(_M("on_interval", frequency_interval=1)))),
+                 ("mani_randomised", _DR()), ("mani_randomised_plate_mass_startup", _DR(PLATE_MASS(_M("on_startup")))),
+                 ("mani_randomised_plate_mass_every_step", _DR(PLATE_MASS(_M("on_interval", frequency_interval=1))))):
+    env = lm.make_env(MANI if name.startswith("mani_") else "QuadrupedPoseControl", num_envs=4096, overrides=ov)
     e = env._task.engine; N = 4096
     g = torch.Generator(device="cuda").manual_seed(0)
     pool = [torch.rand(N, 12, device="cuda", generator=g) * 2 - 1 for _ in range(16)]
@@ -31,8 +43,13 @@ for name, ov in (("plain", None), ("randomised", {"task": {"domain_randomization
     torch.cuda.synchronize(); res[name] = (time.perf_counter() - t0) / 500 * 1e6
     resets[name] = (int(e.cnt[5].sum().item()) - ep0) / 500
     env.close()
-print(json.dumps({"us_per_step": res, "overhead": res["randomised"] / res["plain"] - 1,
-                  "material_overhead_on_k_step_dr": res["randomised_material"] / res["randomised"] - 1,
-                  "reset_state_overhead_on_k_step_dr": res["randomised_reset_state"] / res["randomised_min_frequency_0"] - 1,
-                  "reset_state_gate_closed_overhead_on_k_step_dr": res["randomised_reset_state_gate_closed"] / res["randomised"] - 1,
+ratio = lambda a, b: res[a] / res[b] - 1
+print(json.dumps({"us_per_step": res, "overhead": ratio("randomised", "plain"),
+                  "material_overhead_on_k_step_dr": ratio("randomised_material", "randomised"),
+                  "reset_state_overhead_on_k_step_dr": ratio("randomised_reset_state", "randomised_min_frequency_0"),
+                  "reset_state_gate_closed_overhead_on_k_step_dr": ratio("randomised_reset_state_gate_closed", "randomised"),
+                  "body_masses_startup_overhead_on_k_step_dr": ratio("randomised_body_masses_startup", "randomised"),
+                  "body_masses_every_step_overhead_on_k_step_dr": ratio("randomised_body_masses_every_step", "randomised"),
+                  "plate_mass_startup_overhead_on_k_step_dr": ratio("mani_randomised_plate_mass_startup", "mani_randomised"),
+                  "plate_mass_every_step_overhead_on_k_step_dr": ratio("mani_randomised_plate_mass_every_step", "mani_randomised"),
                   "resets_per_step": resets}))
