@@ -121,6 +121,21 @@ typedef struct lm_mass_dr { lm_dr_channel ch[LM_DR_MASS_CHANNELS];
                             float body_p0[LM_NUM_BODIES], body_p1[LM_NUM_BODIES]; /* table order */ } lm_mass_dr;
 #define LM_DR_MASS_ROWS 23   /* float [row][N]: plate mass, plate inertia factor, 21 body masses (table order): what the last step used, floored */
 
+/* Contact-force reporting, opt-in per engine with lm_enable_contact_forces.  The record is float [LM_CONTACT_ROWS][N]:
+ *   rows 3*l + c   force on foot l (limb order of the state, 0..3) BY THE OTHER SURFACE - the ground in locomotion blocks, the plate in
+ *                  manipulation blocks - component c (x, y, z) in the WORLD frame, in newtons, averaged over the sub-steps of the launch:
+ *                    F_l = 1 / (n_sub dt) * sum over the sub-steps of  R_b (lam_n C0 + lam_1 C1 + lam_2 C2)
+ *                  lam = the impulses the contact solve returned in the LAST pass of that sub-step (the second drive pass where it runs),
+ *                  C0, C1, C2 = that sub-step's contact axes in hub coordinates, R_b = the base's orientation (the fixed one in manipulation
+ *                  blocks).  In the world frame the axes are: locomotion n = (0, 0, 1), t1 = the base's x axis projected onto the ground and
+ *                  normalised, t2 = n x t1; manipulation n = sg x (plate z axis), pointing from the plate to the robot's side, t1 = the plate's
+ *                  x axis, t2 = n x t1 (the kernels evaluate the sum in this form).  Neither clamped nor filtered
+ *   rows 12 + l    contact fraction of foot l: the share of those sub-steps with lam_n > 0, a multiple of 1 / n_sub
+ * n_sub = the sub-steps the launch ran: params.substeps for lm_step, n for lm_substeps(h, targets, n); lm_post_physics (no sub-step) and
+ * lm_substeps(.., 0) leave the record as it was.  An env that lm_step resets reports the sub-steps after its reset (all of them).  The record
+ * is a derived output of the last launch, not state: nothing reads it back, and a checkpoint (Engine.state_dict) does not carry it. */
+#define LM_CONTACT_ROWS 16
+
 typedef struct lm_params {
   int32_t abi_version;     /* LM_ABI_VERSION of the header the caller was compiled against */
   int32_t params_size;     /* the caller's sizeof(lm_params) */
@@ -199,8 +214,11 @@ typedef enum {
                            gravity 3, base force 3, joint damping 12, mu_env 1 (row LM_DR_PHYS_MU) */
   LM_PTR_DR_RESET_STATE = 10, /* float [LM_DR_RESET_ROWS][N]  the state each env was last reset to by lm_step (nominal resets included);
                            randomised engines only (NULL otherwise) */
-  LM_PTR_DR_MASS = 11   /* float [LM_DR_MASS_ROWS][N]  plate mass, plate inertia factor and the 21 body masses (table order) the last step used;
+  LM_PTR_DR_MASS = 11,  /* float [LM_DR_MASS_ROWS][N]  plate mass, plate inertia factor and the 21 body masses (table order) the last step used;
                            the nominal values until a mass channel draws; randomised engines only (NULL otherwise) */
+  LM_PTR_CONTACT = 12   /* float [LM_CONTACT_ROWS][N]  per-foot contact forces and contact fractions of the last reporting launch; NULL until
+                           lm_enable_contact_forces(h, 1).  One more row of N floats follows it, all bits set, which no kernel writes (a guard
+                           the tests read) */
 } lm_ptr_kind;
 
 /* Create an engine for n_envs environments on the current HIP device.
@@ -232,6 +250,20 @@ int lm_set_reset_randomization(lm_engine* h, int block, const lm_reset_dr* rd);
  * non-positive bounds; a uniform / log-uniform range that reaches a non-positive mass (or density factor); a plate channel on a locomotion
  * block.  Synchronous (a blocking copy): call it before the first step and not while a graph that contains lm_step is being captured. */
 int lm_set_mass_randomization(lm_engine* h, int block, const lm_mass_dr* md);
+
+/* Contact-force reporting on (on != 0) or off (0, the state after lm_create); see LM_CONTACT_ROWS.  The first enable allocates the record
+ * and zeroes it; later calls only flip the switch (the record keeps its contents while reporting is off: nothing writes it then).
+ * With reporting on, lm_step and lm_substeps launch builds of their kernels that also write the record (k_step_cf, k_step_pd_cf,
+ * k_step_dr_cf, k_step_dr_pd_cf, k_substeps_cf: every family, both blocks of a co-training engine) - still one launch, no atomics; with it off
+ * they launch exactly the kernels they launched before this entry point existed.  An un-randomised locomotion engine above the k_step_w2
+ * threshold (see lm_step) runs the one-wavefront reporting kernel while reporting is on: the two-wavefront build does not report.
+ * Rollouts (lm_policy.h): LM_ROLLOUT_PERSISTENT returns -1 while reporting is on (the persistent kernel does not report), LM_ROLLOUT_AUTO
+ * picks the graph, LM_ROLLOUT_ENQUEUE and LM_ROLLOUT_GRAPH leave the LAST step's record in the buffer.  A rollout plan created before the
+ * switch stays valid: its graph is re-captured on the next run, as after lm_set_seed, so the switch is never refused on account of a plan.
+ * A hipGraph the CALLER captured around lm_step keeps the kernel of capture time.
+ * LM_EINVAL: null handle, or the calling thread's current device is not the engine's.  Synchronous (allocation, blocking clear): not to be
+ * called while a graph that contains lm_step is being captured. */
+int lm_enable_contact_forces(lm_engine* h, int on);
 
 /* One VecEnvRLGames.step(): reset flagged envs, clamp + apply actions, controlFrequencyInv physics
  * sub-steps, observations / reward / termination.  (vec_env_rlgames.py:56-79)

@@ -107,6 +107,8 @@ struct lm_engine {
   float h_body_mass[LM_NUM_BODIES];      // nominal body masses in table order (what lm_set_mass_randomization checks ranges against)
   float *d_obs, *d_states, *d_rew, *d_extras, *d_terms; long long* d_acc; int acc_rows;
   bool view_obs, view_states, view_terms;      // lm_ptr() handed out obs_buf / states_buf / the reward terms: lm_step keeps them current from then on
+  float* d_contact;        // [LM_CONTACT_ROWS][N] contact record, allocated by the first lm_enable_contact_forces(h, 1) (LM_PTR_CONTACT)
+  bool contact_on;         // lm_step / lm_substeps launch the *_cf kernels and write d_contact
   char* d_stats;           // int64 {num_successes, num_resets} x {all, first task, second task}; float success_rate x 3 at byte 48;
                            // uint32 count of contained blow-ups at byte 60
   lm_params h_params[2];
@@ -583,9 +585,11 @@ LM_DEV SI plate_inertia_env(const lm_params* __restrict__ P, float m, float s) {
 
 // One physics sub-step of one env (4 lanes).  MODE 0: F is the robot base.  MODE 1: F is the plate, the
 // robot base is fixed at (Rb, pb).
-template <int MODE, int VAR, int DR>
+// CF 1 (the contact-force reporting kernels): cf[0..2] += the world-frame contact impulse on this lane's foot, cf[3] += 1 when
+// the foot is loaded (lam_n > 0), both from the impulses of the sub-step's last pass.
+template <int MODE, int VAR, int DR, int CF = 0>
 LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const float* tl, int limb, const Stash& St,
-                    FreeBody& F, const M3& Rfix, V3 pfix, float q[3], float qd[3], const float tgt[3], float tau_acc[3], const DrPhys& X) {
+                    FreeBody& F, const M3& Rfix, V3 pfix, float q[3], float qd[3], const float tgt[3], float tau_acc[3], const DrPhys& X, float* cf = nullptr) {
   const float dt = P->dt, kd = P->kd;
   const float cjv[3] = {VAR ? (DR ? X.cj[0] : P->joint_damping) : 0.f, VAR ? (DR ? X.cj[1] : P->joint_damping) : 0.f, VAR ? (DR ? X.cj[2] : P->joint_damping) : 0.f};
   const float tmax[3] = {DR ? X.tmax[0] : P->tau_max, DR ? X.tmax[1] : P->tau_max, DR ? X.tmax[2] : P->tau_max};
@@ -721,7 +725,7 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
       sat[a] = hi_ || lo_; tsat[a] = hi_ ? tmax[a] : -tmax[a];
     }
   }
-  float qdn[3]; SV un;
+  float qdn[3]; SV un; float lamc[3] = {0.f, 0.f, 0.f};
   for (int pass = 0; pass < 2; pass++) {
     asm volatile("" ::: "memory");          // keep the stash reloads inside the pass (no hoisting across the PGS loop)
     S6 Fq0, Fq1, Fq2; float isc_xz = 0.f, isc_yz = 0.f;
@@ -852,6 +856,7 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
     PgsState S; pgs_setup(S, limb, DR ? mu_dr : P->mu, bn, vf, Wl, T, X);
     pgs_sweeps(S, 0, P->pgs_iters);
     pgs_finish(S, DR ? mu_dr : P->mu, X, lam, w);
+    if (CF) { lamc[0] = lam[0]; lamc[1] = lam[1]; lamc[2] = lam[2]; }
     un = sv(v3(v0f[0] + w[0], v0f[1] + w[1], v0f[2] + w[2]), v3(v0f[3] + w[3], v0f[4] + w[4], v0f[5] + w[5]));
 #pragma unroll
     for (int a = 0; a < 3; a++) qdn[a] = qdf[a] + JH[0][a] * lam[0] + JH[1][a] * lam[1] + JH[2][a] * lam[2];
@@ -892,9 +897,37 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
     float v = fminf(fmaxf(qdn[a], -vm), vm);
     qd[a] = v; q[a] = fmaf(dt, v, q[a]);
   }
+  if (CF) {
+    // the contact axes again, in the world frame (R_b C_r of the hub-coordinate axes above), from Rf / sg of the state before the sub-step: nine
+    // registers less across the pass loop than keeping C0, C1, C2.  Locomotion: R_b C0 = z exactly, R_b C1 = the base's x axis without its z part
+    // Every product-sum below is an explicit fmaf: an expression like a b - c d can be contracted two ways, and the records of k_step_cf and
+    // k_substeps_cf must agree bit for bit whatever the compiler would choose in either
+    if (MODE == 0) {
+      const float s = rsqrtf(fmaxf(fmaf(-Rf.c0.z, Rf.c0.z, 1.0f), 1.0e-12f));
+      cf[0] = fmaf(s, fmaf(lamc[1], Rf.c0.x, -(lamc[2] * Rf.c0.y)), cf[0]);
+      cf[1] = fmaf(s, fmaf(lamc[1], Rf.c0.y, lamc[2] * Rf.c0.x), cf[1]);
+      cf[2] += lamc[0];
+    } else {
+      const float sg = (mulT(Rf, pfix - F.p).z - P->plate_center[2] >= 0.f) ? 1.f : -1.f;      // n = sg x plate z, t1 = plate x, t2 = n x t1 = sg x plate y
+      const float ln = sg * lamc[0], l2 = sg * lamc[2];
+      cf[0] += fmaf(ln, Rf.c2.x, fmaf(lamc[1], Rf.c0.x, l2 * Rf.c1.x));
+      cf[1] += fmaf(ln, Rf.c2.y, fmaf(lamc[1], Rf.c0.y, l2 * Rf.c1.y));
+      cf[2] += fmaf(ln, Rf.c2.z, fmaf(lamc[1], Rf.c0.z, l2 * Rf.c1.z));
+    }
+    cf[3] += lamc[0] > 0.f ? 1.f : 0.f;
+  }
   F.u = un;
   integrate_free(F, Rf, dt);
   LM_STAMP(5);
+}
+
+// the contact record of a launch (LM_PTR_CONTACT, float [LM_CONTACT_ROWS][N]): the mean force on this lane's foot over the n sub-steps it ran and
+// the share of them with the foot loaded.  Lanes of one limb write 16 consecutive envs of a row: four stores per lane, 16 row segments per wavefront
+LM_DEV void store_contact(float* rec, int N, int env, int limb, bool active, const float cf[4], int n, float dt) {
+  if (!active || n <= 0) return;
+  const float sc = 1.0f / ((float)n * dt);
+  rec[(size_t)(3 * limb + 0) * N + env] = cf[0] * sc; rec[(size_t)(3 * limb + 1) * N + env] = cf[1] * sc; rec[(size_t)(3 * limb + 2) * N + env] = cf[2] * sc;
+  rec[(size_t)(12 + limb) * N + env] = (float)((double)cf[3] / (double)n);      // exactly rounded k / n (the build's fp32 division is the 1-ulp reciprocal)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1264,9 +1297,11 @@ struct StepArgs {
                                     // reset to (k_step_dr / k_step_dr_pd only; kept last so that no other member moves)
   const lm_mass_dr* mass_dr;        // mass channels of the two blocks, followed by float [LM_DR_MASS_ROWS][N]: the masses the last step used
                                     // (k_step_dr / k_step_dr_pd only; appended for the same reason)
+  void* reserved;                   // unused: with it the arguments that follow StepArgs (k_substeps, k_fk, k_rollout ...) keep their 16-byte phase, so those kernels' code stays as it was
+  float* contact;                   // [LM_CONTACT_ROWS][N] contact record (the *_cf kernels only; NULL unless reporting is on; appended for the same reason)
 };
 
-template <int MODE, int VAR, int DR, int DEFER = 0>
+template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0>
 LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float* sTab, float* sObs, float* sSt, float4* sStash) {
   TableRegs TR; table_fetch(A.table, threadIdx.x, TR);
   const int lane = threadIdx.x, limb = lane & 3, envl = lane >> 2;
@@ -1430,6 +1465,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
   float tau_acc[3] = {0.f, 0.f, 0.f}, tgtq[3] = {0.f, 0.f, 0.f}, qda[3] = {0.f, 0.f, 0.f}; bool qda_set = false;
   constexpr bool pd = (VAR >= 1);
   const int nsub = (A.nsub < 0) ? P->substeps : A.nsub;
+  float cf[4] = {0.f, 0.f, 0.f, 0.f};      // CF: contact impulse (world) and loaded sub-steps of this lane's foot
   if (!pd) {
     // ---- take_action (robot.py:452-454): velocity targets
     // velocity mode (every task of the path): the drive's velocity target; effort mode: the torque; position mode (robot.py:448-450):
@@ -1438,7 +1474,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
     const bool posm = P->drive_mode == LM_DRIVE_POSITION; const float gp = posm ? P->pd_kp / P->kd : 0.f;
     for (int s = 0; s < nsub; s++) {
       const float tgt[3] = {posm ? gp * (a0[0] - q[0]) : a0[0], posm ? gp * (a0[1] - q[1]) : a0[1], posm ? gp * (a0[2] - q[2]) : a0[2]};
-      substep<MODE, VAR, DR>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X);
+      substep<MODE, VAR, DR, CF>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X, cf);
     }
   } else {
     // ---- custom-controller tasks (quadruped_pose_control_custom_controller.py:255-307): the action integrates the swing / extension
@@ -1459,9 +1495,10 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
       // trailing acc_substeps (= controlFrequencyInv) sub-steps (robot.py:289-291)
       if (s == nsub - P->acc_substeps) { qda[0] = qd[0]; qda[1] = qd[1]; qda[2] = qd[2]; qda_set = true; }
       float tgt[3] = {g * (tgtq[0] - q[0]), g * (tgtq[1] - q[1]), g * (tgtq[2] - q[2])};
-      substep<MODE, VAR, DR>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X);
+      substep<MODE, VAR, DR, CF>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X, cf);
     }
   }
+  if (CF) store_contact(A.contact, N, env, limb, active, cf, nsub, P->dt);      // nsub = 0 (lm_post_physics): the record is left as it was
   // ---- task-layer state (loaded after the physics: issuing these loads at the top of the last sub-step was measured and gains nothing)
   TaskState S; int episode; float lqd[3];
   S.succ = (int)cnt[0 * (size_t)N + env]; S.consec = (int)cnt[1 * (size_t)N + env]; S.greset = (int)cnt[2 * (size_t)N + env];
@@ -1645,6 +1682,32 @@ __global__ void __launch_bounds__(64) k_step_dr_pd(StepArgs A) {
   LM_STEP_SMEM(LM_MAX_OBS)
   if (kind == 2) step_body<0, 1, 1>(A, P, sTab, sObs, sSt, sStash); else if (kind == 3) step_body<1, 1, 1>(A, P, sTab, sObs, sSt, sStash);
   else if (kind == 4) step_body<0, 2, 1>(A, P, sTab, sObs, sSt, sStash); else step_body<1, 2, 1>(A, P, sTab, sObs, sSt, sStash);
+}
+
+// the same four kernels with contact-force reporting (lm_enable_contact_forces): kernels of their own, so that an engine that
+// did not opt in runs the code above unchanged.  The randomised pair too: a wave-uniform switch inside k_step_dr / k_step_dr_pd would keep the
+// four accumulators and the saved impulses allocated in kernels that already fill their 256 VGPRs and spill scalar registers, whether reporting is on or not
+// (new kernels: 4 more AGPRs each; the switch would cost the kernels without reporting those too)
+__global__ void __launch_bounds__(64) k_step_cf(StepArgs A) {
+  LM_STEP_SMEM(64)
+  if (kind == 0) step_body<0, 0, 0, 0, 1>(A, P, sTab, sObs, sSt, sStash); else step_body<1, 0, 0, 0, 1>(A, P, sTab, sObs, sSt, sStash);
+}
+
+__global__ void __launch_bounds__(64) k_step_pd_cf(StepArgs A) {
+  LM_STEP_SMEM(LM_MAX_OBS)
+  if (kind == 2) step_body<0, 1, 0, 0, 1>(A, P, sTab, sObs, sSt, sStash); else if (kind == 3) step_body<1, 1, 0, 0, 1>(A, P, sTab, sObs, sSt, sStash);
+  else if (kind == 4) step_body<0, 2, 0, 0, 1>(A, P, sTab, sObs, sSt, sStash); else step_body<1, 2, 0, 0, 1>(A, P, sTab, sObs, sSt, sStash);
+}
+
+__global__ void __launch_bounds__(64) k_step_dr_cf(StepArgs A) {
+  LM_STEP_SMEM(64)
+  if (kind == 0) step_body<0, 0, 1, 0, 1>(A, P, sTab, sObs, sSt, sStash); else step_body<1, 0, 1, 0, 1>(A, P, sTab, sObs, sSt, sStash);
+}
+
+__global__ void __launch_bounds__(64) k_step_dr_pd_cf(StepArgs A) {
+  LM_STEP_SMEM(LM_MAX_OBS)
+  if (kind == 2) step_body<0, 1, 1, 0, 1>(A, P, sTab, sObs, sSt, sStash); else if (kind == 3) step_body<1, 1, 1, 0, 1>(A, P, sTab, sObs, sSt, sStash);
+  else if (kind == 4) step_body<0, 2, 1, 0, 1>(A, P, sTab, sObs, sSt, sStash); else step_body<1, 2, 1, 0, 1>(A, P, sTab, sObs, sSt, sStash);
 }
 
 
@@ -1888,14 +1951,25 @@ __global__ void __launch_bounds__(64) k_apply_resets_cnt(int64_t* cnt, int N) {
   if (cnt[3 * (size_t)N + i] != 0) { cnt[0 * (size_t)N + i] = 0; cnt[1 * (size_t)N + i] = 0; cnt[2 * (size_t)N + i] = 0; cnt[3 * (size_t)N + i] = 0; cnt[4 * (size_t)N + i] = 0; cnt[5 * (size_t)N + i] += 1; }
 }
 
-template <int MODE>
+// quat_to_mat with the contraction written out the way the compiler contracts it at step_body's world -> body conversion (the w products and
+// the first square of each diagonal sum are the plain multiplies).  In load_phys it contracts y z -+ w x the other way round, which moves the body twist by an ulp: enough to make the
+// contact record of lm_substeps differ from lm_step's in the last bits.  k_substeps_cf loads through this one (XR = 1)
+LM_DEV M3 quat_to_mat_step(float w, float x, float y, float z) {
+  const float wx = w * x, wy = w * y, wz = w * z;
+  M3 R;
+  R.c0 = v3(fmaf(-2.f, fmaf(z, z, y * y), 1.f), 2.f * fmaf(x, y, wz), 2.f * fmaf(x, z, -wy));
+  R.c1 = v3(2.f * fmaf(x, y, -wz), fmaf(-2.f, fmaf(z, z, x * x), 1.f), 2.f * fmaf(y, z, wx));
+  R.c2 = v3(2.f * fmaf(x, z, wy), 2.f * fmaf(y, z, -wx), fmaf(-2.f, fmaf(y, y, x * x), 1.f));
+  return R;
+}
+template <int MODE, int XR = 0>
 LM_DEV void load_phys(const float* st, int N, int env, int limb, FreeBody& F, float q[3], float qd[3]) {
   const int fb = (MODE == 0) ? R_FB0 : R_FB1; const int jj[3] = {limb, 4 + 2 * limb, 5 + 2 * limb};
   F.p = v3(st[(size_t)(fb + 0) * N + env], st[(size_t)(fb + 1) * N + env], st[(size_t)(fb + 2) * N + env]);
   F.q.w = st[(size_t)(fb + 3) * N + env]; F.q.x = st[(size_t)(fb + 4) * N + env]; F.q.y = st[(size_t)(fb + 5) * N + env]; F.q.z = st[(size_t)(fb + 6) * N + env];
   V3 lin = v3(st[(size_t)(fb + 7) * N + env], st[(size_t)(fb + 8) * N + env], st[(size_t)(fb + 9) * N + env]);
   V3 ang = v3(st[(size_t)(fb + 10) * N + env], st[(size_t)(fb + 11) * N + env], st[(size_t)(fb + 12) * N + env]);
-  M3 R = quat_to_mat(F.q.w, F.q.x, F.q.y, F.q.z); F.u = sv(mulT(R, ang), mulT(R, lin));
+  M3 R = XR ? quat_to_mat_step(F.q.w, F.q.x, F.q.y, F.q.z) : quat_to_mat(F.q.w, F.q.x, F.q.y, F.q.z); F.u = sv(mulT(R, ang), mulT(R, lin));
   for (int a = 0; a < 3; a++) { q[a] = st[(size_t)(R_Q + jj[a]) * N + env]; qd[a] = st[(size_t)(R_QD + jj[a]) * N + env]; }
 }
 template <int MODE>
@@ -1911,21 +1985,22 @@ LM_DEV void store_phys(float* st, int N, int env, int limb, const FreeBody& F, c
   }
 }
 
-template <int MODE, int VAR>
+template <int MODE, int VAR, int CF = 0>
 LM_DEV void substeps_body(const StepArgs& A, const lm_params* P, const float* sTab, const float* targets, int n, float4* sStash) {
   const int lane = threadIdx.x, limb = lane & 3, envl = lane >> 2;
   Stash St; St.base = sStash; St.lane = lane;
   const int envr = lm_block() * ENVS_PER_WAVE + envl, N = A.N; const bool active = envr < N; const int env = active ? envr : N - 1;
   const float* tl = sTab + HUB_FLOATS + limb * LIMB_STRIDE; const int jj[3] = {limb, 4 + 2 * limb, 5 + 2 * limb};
   FreeBody F; float q[3], qd[3], tgt[3];
-  load_phys<MODE>(A.state, N, env, limb, F, q, qd);
+  load_phys<MODE, CF>(A.state, N, env, limb, F, q, qd);
   for (int a = 0; a < 3; a++) tgt[a] = targets[(size_t)env * 12 + jj[a]];
   M3 Rfix = quat_to_mat(P->fixed_base_quat[0], P->fixed_base_quat[1], P->fixed_base_quat[2], P->fixed_base_quat[3]);
   V3 pfix = v3(P->fixed_base_pos[0], P->fixed_base_pos[1], P->fixed_base_pos[2]);
   float tau_acc[3] = {0.f, 0.f, 0.f};
-  DrPhys X;
-  for (int s = 0; s < n; s++) substep<MODE, VAR, 0>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X);
+  DrPhys X; float cf[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < n; s++) substep<MODE, VAR, 0, CF>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X, cf);
   if (active) store_phys<MODE>(A.state, N, env, limb, F, q, qd);
+  if (CF) store_contact(A.contact, N, env, limb, active, cf, n, P->dt);
 }
 __global__ void __launch_bounds__(64) k_substeps(StepArgs A, const float* targets, int n) {
   __shared__ __attribute__((aligned(16))) float sTab[LM_ITAB_FLOATS + 2];
@@ -1934,6 +2009,15 @@ __global__ void __launch_bounds__(64) k_substeps(StepArgs A, const float* target
   const lm_params* P = A.params + ((lm_block() * ENVS_PER_WAVE >= A.split) ? 1 : 0);
   if (P->variant == 0) { if (P->mode == LM_MODE_LOCO) substeps_body<0, 0>(A, P, sTab, targets, n, sStash); else substeps_body<1, 0>(A, P, sTab, targets, n, sStash); }
   else { if (P->mode == LM_MODE_LOCO) substeps_body<0, 1>(A, P, sTab, targets, n, sStash); else substeps_body<1, 1>(A, P, sTab, targets, n, sStash); }
+}
+
+__global__ void __launch_bounds__(64) k_substeps_cf(StepArgs A, const float* targets, int n) {      // k_substeps with contact-force reporting
+  __shared__ __attribute__((aligned(16))) float sTab[LM_ITAB_FLOATS + 2];
+  __shared__ float4 sStash[STASH_SLOTS * 64];
+  load_table(A.table, sTab, threadIdx.x);
+  const lm_params* P = A.params + ((lm_block() * ENVS_PER_WAVE >= A.split) ? 1 : 0);
+  if (P->variant == 0) { if (P->mode == LM_MODE_LOCO) substeps_body<0, 0, 1>(A, P, sTab, targets, n, sStash); else substeps_body<1, 0, 1>(A, P, sTab, targets, n, sStash); }
+  else { if (P->mode == LM_MODE_LOCO) substeps_body<0, 1, 1>(A, P, sTab, targets, n, sStash); else substeps_body<1, 1, 1>(A, P, sTab, targets, n, sStash); }
 }
 
 __global__ void __launch_bounds__(64) k_fk(StepArgs A, float* tips, float* knees) {
@@ -2181,7 +2265,7 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
 
 int lm_destroy(lm_engine* h) {
   if (!h) return LM_OK;
-  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_reset_dr, h->d_mass_dr, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats};
+  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_reset_dr, h->d_mass_dr, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats, h->d_contact};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   delete h;
   return LM_OK;
@@ -2202,6 +2286,7 @@ static StepArgs make_args(lm_engine* h, const float* actions, const float* goal_
   A.W.stats = (char*)h->d_stats; A.W.extras = h->d_extras; A.W.out_extras = nullptr; A.W.split_block = h->split / ENVS_PER_WAVE; A.W.acc_rows = h->acc_rows;
   A.W.out_obs = out_obs; A.W.out_states = out_states; A.W.out_rew = out_rew; A.W.out_resets = out_resets;
   A.N = h->N; A.split = h->split; A.seed = h->seed; A.skip_reset = 0; A.nsub = -1; A.drc = h->d_drc; A.dr_phys = h->d_dr_phys; A.reset_dr = h->d_reset_dr; A.mass_dr = h->d_mass_dr;
+  A.reserved = nullptr; A.contact = h->contact_on ? h->d_contact : nullptr;
   for (int t = 0; t < 2; t++) A.kind[t] = h->h_params[t].variant * 2 + (h->h_params[t].mode == LM_MODE_MANI ? 1 : 0);
   return A;
 }
@@ -2227,9 +2312,10 @@ int lm_step(lm_engine* h, const float* actions, const float* goal_rand, float* o
   StepArgs A = make_args(h, actions, goal_rand, out_obs, out_states, out_rew, out_resets); A.W.out_extras = out_extras;
   drop_unrequested_views(h, A);
   const bool pd = A.kind[0] >= 2;                                  // both blocks are of one actuator family (lm_create)
-  if (!h->dr_enabled && A.kind[0] == 0 && A.kind[1] == 0 && h->N >= h->w2_min_envs) lm_internal_launch_step_w2(&A, h->nblocks, s);      // locomotion, two wavefronts per SIMD: ahead beyond 32 768 envs
+  if (!h->contact_on && !h->dr_enabled && A.kind[0] == 0 && A.kind[1] == 0 && h->N >= h->w2_min_envs) lm_internal_launch_step_w2(&A, h->nblocks, s);      // locomotion, two wavefronts per SIMD: ahead beyond 32 768 envs
   else {
-    void (*kern)(StepArgs) = h->dr_enabled ? (pd ? k_step_dr_pd : k_step_dr) : (pd ? k_step_pd : k_step);
+    void (*kern)(StepArgs) = h->contact_on ? (h->dr_enabled ? (pd ? k_step_dr_pd_cf : k_step_dr_cf) : (pd ? k_step_pd_cf : k_step_cf))      // with reporting: one-wavefront kernels at every size
+                                           : (h->dr_enabled ? (pd ? k_step_dr_pd : k_step_dr) : (pd ? k_step_pd : k_step));
     hipLaunchKernelGGL(kern, dim3(h->nblocks), dim3(64), 0, s, A);
   }
   HIPCHK(hipGetLastError());
@@ -2312,6 +2398,20 @@ int lm_set_mass_randomization(lm_engine* h, int block, const lm_mass_dr* md) {
   return LM_OK;
 }
 
+int lm_enable_contact_forces(lm_engine* h, int on) {
+  if (!h) return fail(LM_EINVAL, "lm_enable_contact_forces: null handle");
+  CHECK_DEVICE(h, "lm_enable_contact_forces");
+  if (on && !h->d_contact) {
+    const size_t row = (size_t)h->N * sizeof(float), bytes = LM_CONTACT_ROWS * row;
+    float* p = nullptr;
+    HIPCHK(hipMalloc((void**)&p, bytes + row));      // one guard row behind the record: all bits set, written by no kernel (the tests read it)
+    if (hipMemset(p, 0, bytes) != hipSuccess || hipMemset((char*)p + bytes, 0xFF, row) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(p); return fail(LM_EHIP, "lm_enable_contact_forces: clearing the record failed"); }
+    h->d_contact = p;
+  }
+  h->contact_on = on != 0;
+  return LM_OK;
+}
+
 int lm_reset_all(lm_engine* h, void* stream) {
   if (!h) return fail(LM_EINVAL, "lm_reset_all: null handle");
   CHECK_DEVICE(h, "lm_reset_all");
@@ -2346,7 +2446,7 @@ int lm_substeps(lm_engine* h, const float* targets, int n, void* stream) {
   if (!h || !targets || n < 0) return fail(LM_EINVAL, "lm_substeps: bad argument");
   CHECK_DEVICE(h, "lm_substeps");
   StepArgs A = make_args(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  hipLaunchKernelGGL(k_substeps, dim3(h->nblocks), dim3(64), 0, (hipStream_t)stream, A, targets, n);
+  hipLaunchKernelGGL(h->contact_on ? k_substeps_cf : k_substeps, dim3(h->nblocks), dim3(64), 0, (hipStream_t)stream, A, targets, n);
   HIPCHK(hipGetLastError());
   return LM_OK;
 }
@@ -2385,6 +2485,7 @@ void* lm_ptr(lm_engine* h, int kind) {
     case LM_PTR_EXTRAS: return h->d_extras;
     case LM_PTR_STATS: return h->d_stats;
     case LM_PTR_TERMS: h->view_terms = true; return h->d_terms;
+    case LM_PTR_CONTACT: return h->d_contact;
     default: return nullptr;
   }
 }
@@ -2398,6 +2499,7 @@ int lm_set_seed(lm_engine* h, uint32_t seed) { if (!h) return fail(LM_EINVAL, "l
 int lm_internal_rollout(lm_engine* h, int policy, const LmRolloutArgs& R, hipStream_t s) {
   if (!h || !R.params || !R.log_std || !R.obs || !R.actions || !R.logp || !R.values || !R.rewards || !R.dones || !R.acc_steps || R.T <= 0) return -1;
   if (h->dr_enabled || R.nobs != h->num_obs) return fail(-1, "persistent rollout: domain-randomised engines and foreign observation widths run through the graph mode");
+  if (h->contact_on) return fail(-1, "persistent rollout: an engine with contact-force reporting on runs through the graph mode");
   if (!on_device(h)) return fail(-1, "persistent rollout: the calling thread's current device is not the engine's device");
   StepArgs A = make_args(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   if (!h->view_obs) A.W.obs_buf = nullptr;           // as the graph mode's lm_step(out_obs = the rollout's slot, out_states = NULL) does
@@ -2416,12 +2518,12 @@ int lm_internal_rollout(lm_engine* h, int policy, const LmRolloutArgs& R, hipStr
 }
 
 int lm_internal_rollout_supported(const lm_engine* h, int policy, int nobs) {
-  if (!h || h->dr_enabled || nobs != h->num_obs) return 0;
+  if (!h || h->dr_enabled || h->contact_on || nobs != h->num_obs) return 0;
   return (policy == LM_POLICY_MLP && (nobs == 64 || nobs == LM_MAX_OBS)) || (policy == LM_POLICY_GNN && nobs == 64);
 }
 
 uint64_t lm_internal_args_key(const lm_engine* h) {
-  return h ? ((uint64_t)h->seed | ((uint64_t)((h->view_obs ? 1 : 0) | (h->view_states ? 2 : 0) | (h->view_terms ? 4 : 0)) << 32)) : 0ull;
+  return h ? ((uint64_t)h->seed | ((uint64_t)((h->view_obs ? 1 : 0) | (h->view_states ? 2 : 0) | (h->view_terms ? 4 : 0) | (h->contact_on ? 8 : 0)) << 32)) : 0ull;
 }
 int lm_internal_fail(int code, const char* msg) { return fail(code, msg); }
 #endif      // !LM_W2_UNIT

@@ -172,7 +172,7 @@ int lm_rollout_run(lm_rollout* r, int use_graph, void* stream) {
   if (!r) return lm_internal_fail(-1, "lm_rollout_run: null plan");
   hipStream_t s = (hipStream_t)stream;
   if (use_graph == LM_ROLLOUT_AUTO)      // a persistent block holds a whole CU (512 registers per lane): one resident generation of blocks, or the graph
-    use_graph = (r->persistent_ok && (r->N + 15) / 16 <= r->n_cu) ? LM_ROLLOUT_PERSISTENT : LM_ROLLOUT_GRAPH;
+    use_graph = (r->persistent_ok && lm_internal_rollout_supported(r->env, r->policy, r->nobs) && (r->N + 15) / 16 <= r->n_cu) ? LM_ROLLOUT_PERSISTENT : LM_ROLLOUT_GRAPH;      // asked again: contact-force reporting may have been switched on since
   if (!use_graph) return rollout_enqueue(r, s);
   if (use_graph == LM_ROLLOUT_PERSISTENT) {
     // the whole rollout in one kernel (un-randomised engines); same results as the other two modes
@@ -180,7 +180,7 @@ int lm_rollout_run(lm_rollout* r, int use_graph, void* stream) {
     R.rewards = r->rewards; R.extras = r->extras; R.dones = r->dones; R.acc_steps = r->acc_steps; R.T = r->T; R.nobs = r->nobs; R.noise_seed = r->seed;
     return lm_internal_rollout(r->env, r->policy, R, s);
   }
-  if (r->exec && r->exec_env_key != lm_internal_args_key(r->env)) {      // lm_set_seed / a first lm_ptr() for a view since the capture: the graph's kernel arguments are stale
+  if (r->exec && r->exec_env_key != lm_internal_args_key(r->env)) {      // lm_set_seed / a first lm_ptr() for a view / lm_enable_contact_forces since the capture: the graph's kernel arguments are stale
     (void)hipGraphExecDestroy(r->exec); r->exec = nullptr;
   }
   if (!r->exec) {

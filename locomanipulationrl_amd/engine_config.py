@@ -235,6 +235,9 @@ class EngineParams:
     vel_iters: int = 0
     drive_iter_impulse: float = -1.0
     tgs_flags: int = 0
+    # ---- per-foot contact-force reporting (sim.engine.contact_forces): not part of the C parameter block - the task switches it on
+    # with Engine.enable_contact_forces() after creating the engine, when any of its blocks asks for it
+    contact_forces: bool = False
     # ---- bookkeeping
     max_reset_counts: int = 2048        # success-rate window (quadruped_pose_control.py:151)
     # values the -1 sentinels above were resolved to ({field: value}).  dataclasses.replace() hands every field back to __init__, the resolved ones

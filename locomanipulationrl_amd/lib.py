@@ -20,10 +20,11 @@ STATE_ROWS, CNT_ROWS, NUM_OBS, NUM_STATES, NUM_ACTIONS, NUM_EXTRAS, TABLE_FLOATS
 DR_PHYS_ROWS, DR_PHYS_MU = 43, 42       # LM_DR_PHYS_ROWS, LM_DR_PHYS_MU
 DR_RESET_CHANNELS, DR_RESET_ROWS = 4, 31      # LM_DR_RESET_CHANNELS, LM_DR_RESET_ROWS
 DR_MASS_CHANNELS, DR_MASS_ROWS, NUM_BODIES = 3, 23, 21      # LM_DR_MASS_CHANNELS, LM_DR_MASS_ROWS, LM_NUM_BODIES
-PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS = range(12)
+CONTACT_ROWS = 16        # LM_CONTACT_ROWS
+PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS, PTR_CONTACT = range(13)
 
 # names of the exported C symbols (checked by tests/test_abi.py against include/lm_engine.h)
-EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass_randomization", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
+EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass_randomization", "lm_enable_contact_forces", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
            "lm_forward_kinematics", "lm_debug_dynamics", "lm_ptr", "lm_num_envs", "lm_num_obs", "lm_set_seed", "lm_last_error", "lm_version", "lm_abi_version",
            "lm_gnn_param_count", "lm_gnn_forward", "lm_mlp_param_count", "lm_mlp_forward", "lm_mlp_param_count_obs", "lm_mlp_forward_obs",
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy"]
@@ -205,6 +206,7 @@ def load_library() -> C.CDLL:
     lib.lm_destroy.argtypes = [vp]
     lib.lm_set_reset_randomization.argtypes = [vp, ip, C.POINTER(LmResetDr)]
     lib.lm_set_mass_randomization.argtypes = [vp, ip, C.POINTER(LmMassDr)]
+    lib.lm_enable_contact_forces.argtypes = [vp, ip]
     lib.lm_step.argtypes = [vp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.lm_post_physics.argtypes = [vp, fp, fp, fp, fp, fp, fp, vp]
     lib.lm_reset_all.argtypes = [vp, vp]
@@ -349,6 +351,34 @@ class Engine:
     def dr_body_masses(self):
         """float [21][N]: rows 2..22 of dr_mass (table order)."""
         return self.dr_mass[2:]
+
+    # ------------------------------------------------------------------ contact-force reporting (DESIGN.md 3.7)
+    def enable_contact_forces(self, on: bool = True):
+        """Switch per-foot contact-force reporting on (or off again): step() and substeps() then also write the contact record, from
+        reporting builds of their kernels; an engine that never asks runs the kernels it always ran.  The record is a derived output
+        of the last step, not part of state_dict()."""
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib.lm_enable_contact_forces(self._h, 1 if on else 0))
+
+    def _contact_record(self):
+        if "contact" not in self._views:
+            ptr = self.lib.lm_ptr(self._h, PTR_CONTACT)
+            if not ptr:
+                raise EngineError("contact forces are not reported by this engine: call enable_contact_forces() first "
+                                  "(task YAML: sim.engine.contact_forces: true)")
+            self._views["contact"] = self.torch.as_tensor(_DevArray(ptr, (CONTACT_ROWS, self.num_envs), "<f4", self), device=self.device)
+        return self._views["contact"]
+
+    @property
+    def contact_forces(self):
+        """float (N, 4, 3), a zero-copy view of the record's SoA rows: the force on each foot (limb order of the state) by the ground /
+        the plate, world frame, newtons, averaged over the sub-steps of the last step() or substeps() call."""
+        return self._contact_record()[:12].T.reshape(self.num_envs, 4, 3)
+
+    @property
+    def contact_fraction(self):
+        """float (N, 4) view: the share of the last step's sub-steps in which each foot was loaded (lam_n > 0), a multiple of 1 / n_sub."""
+        return self._contact_record()[12:16].T
 
     @property
     def blowups(self) -> int:

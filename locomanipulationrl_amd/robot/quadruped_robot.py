@@ -89,6 +89,12 @@ class RobotOmni:
     def knee_positions(self):
         return self._fk()[1]
 
+    @property
+    def tip_contact_forces(self):
+        """(n, 4, 3) world-frame contact force on this robot's feet over the last control step, newtons (get_net_contact_forces of a simulator's
+        tensor API, for the feet - the robot's only colliders); needs sim.engine.contact_forces: true."""
+        return self._engine.contact_forces[self._env_slice]
+
     def update_all_states(self):          # state is always current: nothing to pull from a simulator
         return None
 

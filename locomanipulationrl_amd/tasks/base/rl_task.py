@@ -98,6 +98,8 @@ class RLTask:
         else:
             self.engine = engine_factory(load_model(self.model_asset), params, self._num_envs, self.split_env(), seed,
                                          float(self.clip_obs), float(self.clip_actions))
+        if any(getattr(p, "contact_forces", False) for p in params):      # sim.engine.contact_forces: before the first step
+            self.engine.enable_contact_forces(True)
         self.cleanup()
         return self.engine
 
@@ -117,6 +119,10 @@ class RLTask:
     # task-state views (quadruped_pose_control.py:123-154)
     @property
     def goal_quaternions(self): return self.engine.state[86:90].T
+    @property
+    def contact_forces(self): return self.engine.contact_forces            # (N, 4, 3) world-frame force on each foot, N; needs sim.engine.contact_forces
+    @property
+    def contact_fraction(self): return self.engine.contact_fraction        # (N, 4) share of the step's sub-steps with the foot loaded
     @property
     def last_actions(self): return self.engine.state[50:62].T
     @property

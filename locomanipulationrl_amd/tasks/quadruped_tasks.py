@@ -90,13 +90,14 @@ class _QuadrupedTask(RLTask):
             print(f"[locomanipulationrl_amd] foot friction: nominal (YAML, combined) {mu:.3g} x sim.engine.friction_scale {scale:.3g} = {mu * scale:.3g} "
                   f"(fitted on the reference's PhysX recordings, parity unpinned; set sim.engine.friction_scale: 1.0 for the YAML value)", file=sys.stderr)
         mu *= scale
+        report_contacts = bool(eng.get("contact_forces", False))      # per-foot contact forces from the step launch; off by default
         # nominal materials of the contact-material channels: friction_scale x combine(feet, other) reproduces mu above.  `other` is
         # the ground material where it is combined; elsewhere (the plate, a ground without a material) it carries the scene's default material, so
         # the combine gives mu_body back (1.0 under multiply for the same reason)
         comb = eng.get("friction_combine", "average")
         combined = gnd is not None and kw.get("mode", MODE_LOCO) == MODE_LOCO
         mat_fields = dict(mat_mu_robot=mu_body, mat_mu_other=mu_g if combined else (1.0 if comb == "multiply" else mu_body),
-                          friction_combine=FRICTION_COMBINE.get(comb, -1), friction_scale=scale)
+                          friction_combine=FRICTION_COMBINE.get(comb, -1), friction_scale=scale, contact_forces=report_contacts)
         rd = robot.robot_description
         if rd.control_mode not in ("velocity", "position", "effort"):          # robot.py:323-333
             raise AttributeError(f"Invalid control mode name {rd.control_mode!r}")
