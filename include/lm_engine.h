@@ -120,6 +120,25 @@ enum { LM_DR_MASS_PLATE = 0, LM_DR_MASS_PLATE_DENSITY = 1, LM_DR_MASS_BODIES = 2
 typedef struct lm_mass_dr { lm_dr_channel ch[LM_DR_MASS_CHANNELS];
                             float body_p0[LM_NUM_BODIES], body_p1[LM_NUM_BODIES]; /* table order */ } lm_mass_dr;
 #define LM_DR_MASS_ROWS 23   /* float [row][N]: plate mass, plate inertia factor, 21 body masses (table order): what the last step used, floored */
+/* Actuator channels: per-env drive gains and command latency, drawn inside lm_step for the control step.  They live in a
+ * struct of their own, handed over with lm_set_actuator_randomization, so that lm_params keeps its layout.  interval as for the mass channels
+ * (>= 1 on_interval, 0 on_reset behind dr_min_frequency and nominal before the first gated reset, LM_DR_ON_STARTUP).  One draw per env
+ * (component 0, scalar parameters p0[0] / p1[0]); the random streams are 19, 20, 21.
+ *   LM_DR_ACTUATOR_KP       the position gain of the 12 driven joints, nominal pd_kp.  Variants 1 / 2, and variant 0 in LM_DRIVE_POSITION; there is
+ *                      no position gain in LM_DRIVE_VELOCITY / LM_DRIVE_EFFORT
+ *   LM_DR_ACTUATOR_KD       the velocity gain, nominal kd: the implicit drive damping, the saturation test and the drive torque all use the env's
+ *                      value, and kp / kd is formed per env from the two draws.  Every family except LM_DRIVE_EFFORT (gains off)
+ *   LM_DR_ACTUATOR_LATENCY  command latency in sub-steps, nominal 0, additive or direct: d = clamp(floor(draw), 0, substeps).  In the first d
+ *                      sub-steps of the control step the PD law follows the PREVIOUS command (the swing / extension targets before this step's
+ *                      action was integrated; init_se on a resetting env), from sub-step d on the new one; d = substeps delays the command by a
+ *                      whole control period.  What the task layer reads (the stored targets, the target-error terms, the logged torque - the
+ *                      torque that was applied -, acc_substeps) is unchanged.  Variants 1 / 2 only
+ * A drawn gain is floored at LM_DR_MASS_FLOOR x its nominal (kd must stay positive: the solve uses kp / kd); a uniform / log-uniform range
+ * that reaches a non-positive gain is refused.  One kp and one kd per env, not per joint: that is what the CPU oracle can check. */
+#define LM_DR_ACTUATOR_CHANNELS 3
+enum { LM_DR_ACTUATOR_KP = 0, LM_DR_ACTUATOR_KD = 1, LM_DR_ACTUATOR_LATENCY = 2 };
+typedef struct lm_actuator_dr { lm_dr_channel ch[LM_DR_ACTUATOR_CHANNELS]; } lm_actuator_dr;
+#define LM_DR_ACTUATOR_ROWS 3   /* float [row][N]: kp, kd, latency d (sub-steps) the last step used */
 
 /* Contact-force reporting, opt-in per engine with lm_enable_contact_forces.  The record is float [LM_CONTACT_ROWS][N]:
  *   rows 3*l + c   force on foot l (limb order of the state, 0..3) BY THE OTHER SURFACE - the ground in locomotion blocks, the plate in
@@ -216,9 +235,11 @@ typedef enum {
                            randomised engines only (NULL otherwise) */
   LM_PTR_DR_MASS = 11,  /* float [LM_DR_MASS_ROWS][N]  plate mass, plate inertia factor and the 21 body masses (table order) the last step used;
                            the nominal values until a mass channel draws; randomised engines only (NULL otherwise) */
-  LM_PTR_CONTACT = 12   /* float [LM_CONTACT_ROWS][N]  per-foot contact forces and contact fractions of the last reporting launch; NULL until
+  LM_PTR_CONTACT = 12,  /* float [LM_CONTACT_ROWS][N]  per-foot contact forces and contact fractions of the last reporting launch; NULL until
                            lm_enable_contact_forces(h, 1).  One more row of N floats follows it, all bits set, which no kernel writes (a guard
                            the tests read) */
+  LM_PTR_DR_ACTUATOR = 13 /* float [LM_DR_ACTUATOR_ROWS][N]  kp, kd and the command latency d (sub-steps) the last step used; the nominal values
+                           (pd_kp, kd, 0) until an actuator channel draws; randomised engines only (NULL otherwise) */
 } lm_ptr_kind;
 
 /* Create an engine for n_envs environments on the current HIP device.
@@ -250,6 +271,15 @@ int lm_set_reset_randomization(lm_engine* h, int block, const lm_reset_dr* rd);
  * non-positive bounds; a uniform / log-uniform range that reaches a non-positive mass (or density factor); a plate channel on a locomotion
  * block.  Synchronous (a blocking copy): call it before the first step and not while a graph that contains lm_step is being captured. */
 int lm_set_mass_randomization(lm_engine* h, int block, const lm_mass_dr* md);
+
+/* Actuator randomisation of parameter block `block` (0, or 1 on a two-task engine): validates *ad and copies it to device memory owned by
+ * the handle; later lm_step launches draw from it (see LM_DR_ACTUATOR_CHANNELS above).  All three channels are off after lm_create.
+ * LM_EINVAL: engine without dr_enabled; block out of range; an enabled channel with a bad operation / distribution / interval (below
+ * LM_DR_ON_STARTUP); non-finite parameters; log-uniform with non-positive bounds; a uniform / log-uniform range that reaches a non-positive
+ * gain; LM_DR_ACTUATOR_KP on a variant-0 block that is not in LM_DRIVE_POSITION; LM_DR_ACTUATOR_KD on a block in LM_DRIVE_EFFORT; LM_DR_ACTUATOR_LATENCY on
+ * a variant-0 block, or with LM_DR_SCALING (the nominal is 0).  Synchronous (a blocking copy): call it before the first step and not while a
+ * graph that contains lm_step is being captured. */
+int lm_set_actuator_randomization(lm_engine* h, int block, const lm_actuator_dr* ad);
 
 /* Contact-force reporting on (on != 0) or off (0, the state after lm_create); see LM_CONTACT_ROWS.  The first enable allocates the record
  * and zeroes it; later calls only flip the switch (the record keeps its contents while reporting is off: nothing writes it then).

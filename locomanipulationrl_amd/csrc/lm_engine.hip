@@ -104,6 +104,7 @@ struct lm_engine {
   float* d_state; int64_t* d_cnt; int64_t* d_drc; float* d_dr_phys; int dr_enabled;
   lm_reset_dr* d_reset_dr; // randomised engines: the reset-state channels of the two blocks, followed by float [LM_DR_RESET_ROWS][N] (LM_PTR_DR_RESET_STATE)
   lm_mass_dr* d_mass_dr;   // randomised engines: the mass channels of the two blocks, followed by float [LM_DR_MASS_ROWS][N] (LM_PTR_DR_MASS)
+  lm_actuator_dr* d_actuator_dr;      // randomised engines: the actuator channels of the two blocks, followed by float [LM_DR_ACTUATOR_ROWS][N] (LM_PTR_DR_ACTUATOR)
   float h_body_mass[LM_NUM_BODIES];      // nominal body masses in table order (what lm_set_mass_randomization checks ranges against)
   float *d_obs, *d_states, *d_rew, *d_extras, *d_terms; long long* d_acc; int acc_rows;
   bool view_obs, view_states, view_terms;      // lm_ptr() handed out obs_buf / states_buf / the reward terms: lm_step keeps them current from then on
@@ -197,7 +198,19 @@ LM_DEV float dr_mass(const lm_dr_channel& ch, uint32_t seed, uint32_t stream, in
 struct DrPhys { float tmax[3], vmax[3], cj[3]; V3 g, f; float mu;      // this lane's three joints; gravity (world); base-link force (world); contact mu
                 // mass channels: wave-uniform switches (bodies / plate); masses of the shell, (link4 | link1), (link3 | link2) and the hub; the plate's
                 // mass and the factor on its inertia about the COM.  Read only where the matching switch is on
-                int mb_on, mp_on; float m_s; f2 m_41, m_32; float m_hub, m_plate, s_plate; };
+                int mb_on, mp_on; float m_s; f2 m_41, m_32; float m_hub, m_plate, s_plate;
+                // actuator channels: this env's velocity gain kd and kp / kd (the block's values while the gain channels are off); lat_on: the
+                // latency channel is on (wave-uniform), lat: the sub-steps of this step that still follow the previous command
+                float kd, gk; int lat_on, lat; };
+// actuator channels (include/lm_engine.h, LM_DR_ACTUATOR_CHANNELS): the gains go through dr_mass (floored at LM_DR_MASS_FLOOR x nominal); the
+// latency is operation(0, draw), floored to whole sub-steps and clamped to [0, nsub]
+#define LM_DR_STREAM_ACTUATOR 19U     // streams 19 (kp), 20 (kd), 21 (command latency)
+LM_DEV int dr_latency(const lm_dr_channel& ch, uint32_t seed, int env, uint32_t dr_step, uint32_t reset_key, int nsub) {
+  const uint32_t key = ch.interval > 0 ? dr_step / (uint32_t)ch.interval : (ch.interval < 0 ? 0U : reset_key);
+  if (ch.interval == 0 && key == 0) return 0;
+  const float x = dr_apply(ch.operation, 0.f, dr_sample(seed, LM_DR_STREAM_ACTUATOR + LM_DR_ACTUATOR_LATENCY, (uint32_t)env, key, 0U, ch.distribution, ch.p0[0], ch.p1[0]));
+  return (int)fminf(fmaxf(floorf(x), 0.f), (float)nsub);
+}
 LM_DEV Q4 quat_from_euler(float roll, float pitch, float yaw) {
   float sy, cy, sr, cr, sp, cp;
   sincosf(yaw * 0.5f, &sy, &cy); sincosf(roll * 0.5f, &sr, &cr); sincosf(pitch * 0.5f, &sp, &cp);
@@ -590,7 +603,7 @@ LM_DEV SI plate_inertia_env(const lm_params* __restrict__ P, float m, float s) {
 template <int MODE, int VAR, int DR, int CF = 0>
 LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const float* tl, int limb, const Stash& St,
                     FreeBody& F, const M3& Rfix, V3 pfix, float q[3], float qd[3], const float tgt[3], float tau_acc[3], const DrPhys& X, float* cf = nullptr) {
-  const float dt = P->dt, kd = P->kd;
+  const float dt = P->dt, kd = DR ? X.kd : P->kd;      // DR: this env's velocity gain (the block's kd unless the kd channel drew)
   const float cjv[3] = {VAR ? (DR ? X.cj[0] : P->joint_damping) : 0.f, VAR ? (DR ? X.cj[1] : P->joint_damping) : 0.f, VAR ? (DR ? X.cj[2] : P->joint_damping) : 0.f};
   const float tmax[3] = {DR ? X.tmax[0] : P->tau_max, DR ? X.tmax[1] : P->tau_max, DR ? X.tmax[2] : P->tau_max};
   const float mu_dr = DR ? X.mu : 0.f;      // the DrPhys X is shadowed by the contact rows inside the pass loop
@@ -1299,6 +1312,9 @@ struct StepArgs {
                                     // (k_step_dr / k_step_dr_pd only; appended for the same reason)
   void* reserved;                   // unused: with it the arguments that follow StepArgs (k_substeps, k_fk, k_rollout ...) keep their 16-byte phase, so those kernels' code stays as it was
   float* contact;                   // [LM_CONTACT_ROWS][N] contact record (the *_cf kernels only; NULL unless reporting is on; appended for the same reason)
+  void* reserved2;                  // unused: keeps the 16-byte phase of what follows StepArgs, as `reserved` does
+  const lm_actuator_dr* actuator_dr;      // actuator channels of the two blocks, followed by float [LM_DR_ACTUATOR_ROWS][N]: kp, kd and latency the last
+                                    // step used (the randomised kernels only; the new last member)
 };
 
 template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0>
@@ -1393,6 +1409,24 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
         if (active && limb == 0) { mrec[env] = X.m_plate; mrec[(size_t)N + env] = X.s_plate; }
       }
     }
+    // actuator channels: one kp, one kd and one command latency per env.  The switches are wave-uniform; with the gain channels
+    // off the lanes carry the block's kd and kp / kd, with the latency channel off no sub-step looks at the previous command
+    {
+      const lm_actuator_dr* AD = A.actuator_dr + ((env0 >= A.split) ? 1 : 0);
+      const lm_dr_channel& ckp = AD->ch[LM_DR_ACTUATOR_KP]; const lm_dr_channel& ckd = AD->ch[LM_DR_ACTUATOR_KD]; const lm_dr_channel& cl = AD->ch[LM_DR_ACTUATOR_LATENCY];
+      float* arec = (float*)(A.actuator_dr + 2);
+      X.kd = P->kd; X.gk = P->pd_kp / P->kd; X.lat_on = (VAR >= 1 && cl.enabled) ? 1 : 0; X.lat = 0;
+      if (ckp.enabled || ckd.enabled) {
+        const float kpe = dr_mass(ckp, A.seed, LM_DR_STREAM_ACTUATOR + LM_DR_ACTUATOR_KP, env, dr_step, (uint32_t)dr_reset_key, 0U, ckp.p0[0], ckp.p1[0], P->pd_kp);
+        X.kd = dr_mass(ckd, A.seed, LM_DR_STREAM_ACTUATOR + LM_DR_ACTUATOR_KD, env, dr_step, (uint32_t)dr_reset_key, 0U, ckd.p0[0], ckd.p1[0], P->kd);
+        X.gk = kpe / X.kd;
+        if (active && limb == 0) { arec[env] = kpe; arec[(size_t)N + env] = X.kd; }
+      }
+      if (VAR >= 1 && X.lat_on) {
+        X.lat = dr_latency(cl, A.seed, env, dr_step, (uint32_t)dr_reset_key, (A.nsub < 0) ? P->substeps : A.nsub);
+        if (active && limb == 0) arec[(size_t)2 * N + env] = (float)X.lat;
+      }
+    }
     if (active) {
       float* ph = A.dr_phys;
 #pragma unroll
@@ -1471,7 +1505,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
     // velocity mode (every task of the path): the drive's velocity target; effort mode: the torque; position mode (robot.py:448-450):
     // q* = a * act_scale, tau = kp (q* - q) - kd qd = kd (v* - qd) with v* = kp / kd (q* - q), re-evaluated every sub-step
     const float a0[3] = {act[0] * P->act_scale, act[1] * P->act_scale, act[2] * P->act_scale};
-    const bool posm = P->drive_mode == LM_DRIVE_POSITION; const float gp = posm ? P->pd_kp / P->kd : 0.f;
+    const bool posm = P->drive_mode == LM_DRIVE_POSITION; const float gp = posm ? (DR ? X.gk : P->pd_kp / P->kd) : 0.f;
     for (int s = 0; s < nsub; s++) {
       const float tgt[3] = {posm ? gp * (a0[0] - q[0]) : a0[0], posm ? gp * (a0[1] - q[1]) : a0[1], posm ? gp * (a0[2] - q[2]) : a0[2]};
       substep<MODE, VAR, DR, CF>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X, cf);
@@ -1480,21 +1514,26 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
     // ---- custom-controller tasks (quadruped_pose_control_custom_controller.py:255-307): the action integrates the swing / extension
     // position targets; the actuator torque  clamp(kp (q* - q) - kd qd, +-tau_max)  is re-evaluated every sub-step.  It is the same drive
     // as above with damping gain kd and the position-derived velocity target  v* = kp / kd (q* - q)  (implicit in qd, 2-pass clamp).
-    float se[3];
+    float se[3], sep[3];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
       float v = do_reset ? P->init_se[jj[a]] : st[(size_t)(R_SE + jj[a]) * N + env];
+      sep[a] = v;
       if (!A.skip_reset || A.nsub != 0) v = fminf(fmaxf(v + act[a] * P->act_scale_se, P->se_lo[jj[a]]), P->se_hi[jj[a]]);
       se[a] = v;
       if (active) st[(size_t)(R_SE + jj[a]) * N + env] = v;
     }
     tgtq[0] = se[0]; tgtq[1] = se[1] + 0.5f * se[2]; tgtq[2] = se[1] - 0.5f * se[2];      // dof1, dof2 = swing + ext/2, dof3 = swing - ext/2
-    const float g = P->pd_kp / P->kd;
+    // command latency (DR): the first X.lat sub-steps still follow the previous command, the targets before this step's action
+    const bool lat_on = DR && X.lat_on;
+    const float tgtp[3] = {sep[0], sep[1] + 0.5f * sep[2], sep[1] - 0.5f * sep[2]};
+    const float g = DR ? X.gk : P->pd_kp / P->kd;
     for (int s = 0; s < nsub; s++) {
       // update_joint_states() runs after every in-task sub-step (…custom_controller.py:296-297): the joint acceleration spans only the
       // trailing acc_substeps (= controlFrequencyInv) sub-steps (robot.py:289-291)
       if (s == nsub - P->acc_substeps) { qda[0] = qd[0]; qda[1] = qd[1]; qda[2] = qd[2]; qda_set = true; }
-      float tgt[3] = {g * (tgtq[0] - q[0]), g * (tgtq[1] - q[1]), g * (tgtq[2] - q[2])};
+      const bool prev = lat_on && s < X.lat;
+      float tgt[3] = {g * ((prev ? tgtp[0] : tgtq[0]) - q[0]), g * ((prev ? tgtp[1] : tgtq[1]) - q[1]), g * ((prev ? tgtp[2] : tgtq[2]) - q[2])};
       substep<MODE, VAR, DR, CF>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X, cf);
     }
   }
@@ -2220,6 +2259,7 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
   ALLOC(h->d_dr_phys, LM_DR_PHYS_ROWS * N * sizeof(float));
   if (h->dr_enabled) ALLOC(h->d_reset_dr, 2 * sizeof(lm_reset_dr) + LM_DR_RESET_ROWS * N * sizeof(float));      // zeros: all four channels off
   if (h->dr_enabled) ALLOC(h->d_mass_dr, 2 * sizeof(lm_mass_dr) + LM_DR_MASS_ROWS * N * sizeof(float));         // zeros: all three channels off
+  if (h->dr_enabled) ALLOC(h->d_actuator_dr, 2 * sizeof(lm_actuator_dr) + LM_DR_ACTUATOR_ROWS * N * sizeof(float));      // zeros: all three channels off
   ALLOC(h->d_obs, N * (size_t)h->num_obs * sizeof(float));
   ALLOC(h->d_states, N * 93 * sizeof(float));
   ALLOC(h->d_rew, N * sizeof(float));
@@ -2250,6 +2290,16 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
     delete[] tmp;
     if (e1 != hipSuccess) { lm_destroy(h); return fail(LM_EHIP, "lm_create: initial upload failed"); }
   }
+  if (h->d_actuator_dr) {      // the same for the actuator record: the blocks' gains, no latency
+    float* tmp = new float[LM_DR_ACTUATOR_ROWS * N];
+    for (size_t e = 0; e < N; e++) {
+      const lm_params& pb = h->h_params[(int)e >= h->split ? 1 : 0];
+      tmp[e] = pb.pd_kp; tmp[N + e] = pb.kd; tmp[2 * N + e] = 0.f;
+    }
+    hipError_t e1 = hipMemcpy(h->d_actuator_dr + 2, tmp, LM_DR_ACTUATOR_ROWS * N * sizeof(float), hipMemcpyHostToDevice);
+    delete[] tmp;
+    if (e1 != hipSuccess) { lm_destroy(h); return fail(LM_EHIP, "lm_create: initial upload failed"); }
+  }
   // identity quaternions so that an un-reset state is still valid; reset_buf = 1 (rl_task.py:111)
   {
     float* tmp = new float[LM_STATE_ROWS * N](); int64_t* ct = new int64_t[LM_CNT_ROWS * N]();
@@ -2265,7 +2315,7 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
 
 int lm_destroy(lm_engine* h) {
   if (!h) return LM_OK;
-  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_reset_dr, h->d_mass_dr, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats, h->d_contact};
+  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_reset_dr, h->d_mass_dr, h->d_actuator_dr, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats, h->d_contact};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   delete h;
   return LM_OK;
@@ -2286,7 +2336,7 @@ static StepArgs make_args(lm_engine* h, const float* actions, const float* goal_
   A.W.stats = (char*)h->d_stats; A.W.extras = h->d_extras; A.W.out_extras = nullptr; A.W.split_block = h->split / ENVS_PER_WAVE; A.W.acc_rows = h->acc_rows;
   A.W.out_obs = out_obs; A.W.out_states = out_states; A.W.out_rew = out_rew; A.W.out_resets = out_resets;
   A.N = h->N; A.split = h->split; A.seed = h->seed; A.skip_reset = 0; A.nsub = -1; A.drc = h->d_drc; A.dr_phys = h->d_dr_phys; A.reset_dr = h->d_reset_dr; A.mass_dr = h->d_mass_dr;
-  A.reserved = nullptr; A.contact = h->contact_on ? h->d_contact : nullptr;
+  A.reserved = nullptr; A.contact = h->contact_on ? h->d_contact : nullptr; A.reserved2 = nullptr; A.actuator_dr = h->d_actuator_dr;
   for (int t = 0; t < 2; t++) A.kind[t] = h->h_params[t].variant * 2 + (h->h_params[t].mode == LM_MODE_MANI ? 1 : 0);
   return A;
 }
@@ -2398,6 +2448,35 @@ int lm_set_mass_randomization(lm_engine* h, int block, const lm_mass_dr* md) {
   return LM_OK;
 }
 
+int lm_set_actuator_randomization(lm_engine* h, int block, const lm_actuator_dr* ad) {
+  if (!h || !ad) return fail(LM_EINVAL, "lm_set_actuator_randomization: null argument");
+  if (!h->dr_enabled || !h->d_actuator_dr) return fail(LM_EINVAL, "lm_set_actuator_randomization: the engine was created without dr_enabled");
+  if (block < 0 || block >= h->n_tasks) return fail(LM_EINVAL, "lm_set_actuator_randomization: block must be 0 (or 1 on a two-task engine)");
+  CHECK_DEVICE(h, "lm_set_actuator_randomization");
+  const lm_params& P = h->h_params[block];
+  for (int c = 0; c < LM_DR_ACTUATOR_CHANNELS; c++) {
+    const lm_dr_channel& ch = ad->ch[c];
+    if (!ch.enabled) continue;
+    if (ch.operation < 0 || ch.operation > 2 || ch.distribution < 0 || ch.distribution > 2 || ch.interval < LM_DR_ON_STARTUP)
+      return fail(LM_EINVAL, "lm_set_actuator_randomization: invalid operation / distribution / interval");
+    if (c == LM_DR_ACTUATOR_KP && P.variant == 0 && P.drive_mode != LM_DRIVE_POSITION)
+      return fail(LM_EINVAL, "lm_set_actuator_randomization: the kp channel needs a position gain (variants 1 / 2, or variant 0 in position drive mode)");
+    if (c == LM_DR_ACTUATOR_KD && P.variant == 0 && P.drive_mode == LM_DRIVE_EFFORT)
+      return fail(LM_EINVAL, "lm_set_actuator_randomization: the kd channel has nothing to act on in effort drive mode (gains off)");
+    if (c == LM_DR_ACTUATOR_LATENCY && P.variant == 0)
+      return fail(LM_EINVAL, "lm_set_actuator_randomization: the latency channel exists on the PD-actuator variants (1 / 2) only");
+    if (c == LM_DR_ACTUATOR_LATENCY && ch.operation == LM_DR_SCALING)
+      return fail(LM_EINVAL, "lm_set_actuator_randomization: scaling the command latency is refused (its nominal is 0)");
+    const float p0 = ch.p0[0], p1 = ch.p1[0];
+    if (!std::isfinite(p0) || !std::isfinite(p1)) return fail(LM_EINVAL, "lm_set_actuator_randomization: non-finite distribution parameters");
+    if (ch.distribution == LM_DR_LOGUNIFORM && !(p0 > 0 && p1 > 0)) return fail(LM_EINVAL, "lm_set_actuator_randomization: log-uniform bounds must be positive");
+    if (c != LM_DR_ACTUATOR_LATENCY && !mass_range_ok(ch, p0, p1, c == LM_DR_ACTUATOR_KP ? P.pd_kp : P.kd))
+      return fail(LM_EINVAL, "lm_set_actuator_randomization: the distribution's range reaches a non-positive gain");
+  }
+  HIPCHK(hipMemcpy(h->d_actuator_dr + block, ad, sizeof(lm_actuator_dr), hipMemcpyHostToDevice));
+  return LM_OK;
+}
+
 int lm_enable_contact_forces(lm_engine* h, int on) {
   if (!h) return fail(LM_EINVAL, "lm_enable_contact_forces: null handle");
   CHECK_DEVICE(h, "lm_enable_contact_forces");
@@ -2479,6 +2558,7 @@ void* lm_ptr(lm_engine* h, int kind) {
     case LM_PTR_DR_PHYS: return h->d_dr_phys;
     case LM_PTR_DR_RESET_STATE: return h->d_reset_dr ? (void*)(h->d_reset_dr + 2) : nullptr;
     case LM_PTR_DR_MASS: return h->d_mass_dr ? (void*)(h->d_mass_dr + 2) : nullptr;
+    case LM_PTR_DR_ACTUATOR: return h->d_actuator_dr ? (void*)(h->d_actuator_dr + 2) : nullptr;
     case LM_PTR_OBS_BUF: h->view_obs = true; return h->d_obs;
     case LM_PTR_STATES_BUF: h->view_states = true; return h->d_states;
     case LM_PTR_REW_BUF: return h->d_rew;

@@ -80,6 +80,12 @@ NUM_BODIES = 21
 DR_MASS_ROWS = 23                   # rows of Engine.dr_mass: plate mass, plate inertia factor, 21 body masses in table order
 DR_MASS_FLOOR = 0.05                # a drawn mass is floored at this fraction of its nominal (LM_DR_MASS_FLOOR)
 DR_STREAM_MASS = 16                 # random streams 16 (plate mass), 17 (plate density), 18 (body masses)
+# actuator channels (include/lm_engine.h LM_DR_ACTUATOR_*): per-env drive gains and command latency, drawn in the step launch; they
+# reach the engine through lm_set_actuator_randomization.  interval as for the mass channels; one draw per env (p0[0] / p1[0])
+DR_ACTUATOR_KP, DR_ACTUATOR_KD, DR_ACTUATOR_LATENCY = range(3)
+DR_ACTUATOR_CHANNELS = 3
+DR_ACTUATOR_ROWS = 3                # rows of Engine.dr_actuator: kp, kd, command latency in sub-steps
+DR_STREAM_ACTUATOR = 19             # random streams 19 (kp), 20 (kd), 21 (command latency)
 FRICTION_COMBINE = {"average": 0, "min": 1, "multiply": 2, "max": 3}      # PhysX's PxCombineMode order (LM_COMBINE_*)
 
 
@@ -115,6 +121,10 @@ def _no_reset():
 
 def _no_mass():
     return [DRChannel() for _ in range(DR_MASS_CHANNELS)]
+
+
+def _no_actuator():
+    return [DRChannel() for _ in range(DR_ACTUATOR_CHANNELS)]
 
 
 @dataclass
@@ -222,6 +232,11 @@ class EngineParams:
     dr_mass: List[DRChannel] = field(default_factory=_no_mass)
     dr_mass_body_p0: List[float] = _f([0.0] * NUM_BODIES)
     dr_mass_body_p1: List[float] = _f([0.0] * NUM_BODIES)
+    # actuator channels [kp, kd, command latency]: one draw per env.  The gains are operation(pd_kp | kd, draw), floored at
+    # DR_MASS_FLOOR x nominal; kp needs a position gain (variants 1 / 2, or variant 0 with drive_mode 1), kd anything but drive_mode 2.  The latency
+    # is d = clamp(floor(operation(0, draw)), 0, substeps) sub-steps during which the PD law still follows the previous command (variants 1 / 2 only;
+    # additive | direct).  Not part of the C parameter block
+    dr_actuator: List[DRChannel] = field(default_factory=_no_actuator)
     # ---- RobotOmni.take_action control mode (robot/base/robot.py:444-461), variant 0 only: 0 velocity (every task of the path), 1 position
     # (target a * act_scale rad with act_scale = pi, PD gains pd_kp / kd), 2 effort (torque a * act_scale N m with act_scale = torque limit)
     drive_mode: int = 0

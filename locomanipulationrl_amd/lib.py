@@ -20,11 +20,12 @@ STATE_ROWS, CNT_ROWS, NUM_OBS, NUM_STATES, NUM_ACTIONS, NUM_EXTRAS, TABLE_FLOATS
 DR_PHYS_ROWS, DR_PHYS_MU = 43, 42       # LM_DR_PHYS_ROWS, LM_DR_PHYS_MU
 DR_RESET_CHANNELS, DR_RESET_ROWS = 4, 31      # LM_DR_RESET_CHANNELS, LM_DR_RESET_ROWS
 DR_MASS_CHANNELS, DR_MASS_ROWS, NUM_BODIES = 3, 23, 21      # LM_DR_MASS_CHANNELS, LM_DR_MASS_ROWS, LM_NUM_BODIES
+DR_ACTUATOR_CHANNELS, DR_ACTUATOR_ROWS = 3, 3      # LM_DR_ACTUATOR_CHANNELS, LM_DR_ACTUATOR_ROWS
 CONTACT_ROWS = 16        # LM_CONTACT_ROWS
-PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS, PTR_CONTACT = range(13)
+PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS, PTR_CONTACT, PTR_DR_ACTUATOR = range(14)
 
 # names of the exported C symbols (checked by tests/test_abi.py against include/lm_engine.h)
-EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass_randomization", "lm_enable_contact_forces", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
+EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass_randomization", "lm_set_actuator_randomization", "lm_enable_contact_forces", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
            "lm_forward_kinematics", "lm_debug_dynamics", "lm_ptr", "lm_num_envs", "lm_num_obs", "lm_set_seed", "lm_last_error", "lm_version", "lm_abi_version",
            "lm_gnn_param_count", "lm_gnn_forward", "lm_mlp_param_count", "lm_mlp_forward", "lm_mlp_param_count_obs", "lm_mlp_forward_obs",
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy"]
@@ -76,6 +77,19 @@ def make_mass_dr(ep) -> LmMassDr:
             raise ValueError(f"EngineParams.{name}: {NUM_BODIES} values (table order) are needed, got {len(vals)}")
         for k, x in enumerate(vals):
             dst[k] = float(x)
+    return r
+
+
+class LmActuatorDr(C.Structure):
+    """lm_actuator_dr: the three actuator channels of one parameter block (kp, kd, command latency)."""
+    _fields_ = [("ch", LmDrChannel * DR_ACTUATOR_CHANNELS)]
+
+
+def make_actuator_dr(ep) -> LmActuatorDr:
+    """EngineParams.dr_actuator -> C struct (all channels off for a block that carries none)."""
+    r = LmActuatorDr()
+    for i, ch in enumerate(getattr(ep, "dr_actuator", None) or []):
+        _fill_channel(r.ch[i], ch)
     return r
 
 
@@ -206,6 +220,7 @@ def load_library() -> C.CDLL:
     lib.lm_destroy.argtypes = [vp]
     lib.lm_set_reset_randomization.argtypes = [vp, ip, C.POINTER(LmResetDr)]
     lib.lm_set_mass_randomization.argtypes = [vp, ip, C.POINTER(LmMassDr)]
+    lib.lm_set_actuator_randomization.argtypes = [vp, ip, C.POINTER(LmActuatorDr)]
     lib.lm_enable_contact_forces.argtypes = [vp, ip]
     lib.lm_step.argtypes = [vp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.lm_post_physics.argtypes = [vp, fp, fp, fp, fp, fp, fp, vp]
@@ -279,6 +294,10 @@ class Engine:
                 md = make_mass_dr(ep)
                 with torch.cuda.device(self.device):
                     self._check(self.lib.lm_set_mass_randomization(self._h, b, C.byref(md)))
+            if any(ch.enabled for ch in (getattr(ep, "dr_actuator", None) or [])):          # actuator channels: the same way
+                ad = make_actuator_dr(ep)
+                with torch.cuda.device(self.device):
+                    self._check(self.lib.lm_set_actuator_randomization(self._h, b, C.byref(ad)))
         self.seed = int(seed) & 0xFFFFFFFF
         N = self.num_envs
         self.state = self._wrap(PTR_STATE, (STATE_ROWS, N), "<f4")
@@ -379,6 +398,32 @@ class Engine:
     def contact_fraction(self):
         """float (N, 4) view: the share of the last step's sub-steps in which each foot was loaded (lam_n > 0), a multiple of 1 / n_sub."""
         return self._contact_record()[12:16].T
+
+    @property
+    def dr_actuator(self):
+        """float [3][N]: what the last step used - row 0 the position gain kp, row 1 the velocity gain kd (both floored), row 2 the command
+        latency d in sub-steps.  The nominal values (pd_kp, kd, 0) until an actuator channel draws.  Randomised engines only (dr_enabled)."""
+        if "dr_actuator" not in self._views:
+            ptr = self.lib.lm_ptr(self._h, PTR_DR_ACTUATOR)
+            if not ptr:
+                raise EngineError("dr_actuator: the engine was created without dr_enabled (no actuator record)")
+            self._views["dr_actuator"] = self.torch.as_tensor(_DevArray(ptr, (DR_ACTUATOR_ROWS, self.num_envs), "<f4", self), device=self.device)
+        return self._views["dr_actuator"]
+
+    @property
+    def dr_kp(self):
+        """float [N]: row 0 of dr_actuator."""
+        return self.dr_actuator[0]
+
+    @property
+    def dr_kd(self):
+        """float [N]: row 1 of dr_actuator."""
+        return self.dr_actuator[1]
+
+    @property
+    def dr_latency(self):
+        """float [N]: row 2 of dr_actuator (whole sub-steps)."""
+        return self.dr_actuator[2]
 
     @property
     def blowups(self) -> int:

@@ -162,6 +162,7 @@ class _QuadrupedTask(RLTask):
         ep = EngineParams(**base)
         if ep.mode == MODE_MANI:
             self._dr_randomizer.check_plate_mass_range(ep.plate_mass)          # a plate-mass entry must keep THIS block's plate positive
+        self._dr_randomizer.check_actuator(ep)          # joint_kps / joint_kds / command_latency against THIS block's actuator family and gains
         return ep
 
     def _loco_params(self, robot) -> EngineParams:

@@ -41,6 +41,15 @@ Supported entries (everything the reference's YAMLs enable):
                                                        (EngineParams.dr_mass; DESIGN.md 3.6: drawn inside the step launch, floored at 0.05 x nominal;
                                                        a uniform / loguniform range that reaches a non-positive mass is refused; parity with the
                                                        replicator is unpinned, as for every physics attribute)
+    articulation_views.<robot>.joint_kps               on_startup | on_reset | on_interval, additive | scaling | direct, [a, b]: the position gain of the
+                                                       12 driven joints, ONE draw per env (nominal: the task's kp).  PD-actuator tasks and
+                                                       position control; refused in velocity / effort control (there is no position gain)
+    articulation_views.<robot>.joint_kds               the same for the velocity gain kd; every task except effort control (gains off)
+    articulation_views.<robot>.command_latency         on_startup | on_reset | on_interval, additive | direct, [a, b] in sub-steps: the first
+                                                       d = clamp(floor(draw), 0, sub-steps per step) sub-steps of a control step still follow the
+                                                       previous command.  PD-actuator tasks only
+                                                       (EngineParams.dr_actuator; DESIGN.md 3.6: drawn inside the step launch, gains floored at 0.05 x
+                                                       nominal; a uniform / loguniform range that reaches a non-positive gain is refused)
 Anything else (mass / density of other rigid-prim views - the base link's included: use body_masses -, body_inertias, material_properties of
 other views, stiffness ...) raises NotImplementedError when `randomize: True` - a silently ignored randomisation would be worse than a loud one."""
 from __future__ import annotations
@@ -49,7 +58,7 @@ from typing import List
 
 import numpy as np
 
-from ...engine_config import (DR_ACT_INTERVAL, DR_ACT_RESET, DR_BASE_FORCE, DR_CHANNELS, DR_DISTRIBUTIONS, DR_GRAVITY, DR_JOINT_DAMPING, DR_MAT_OTHER,
+from ...engine_config import (DR_ACT_INTERVAL, DR_ACT_RESET, DR_ACTUATOR_CHANNELS, DR_ACTUATOR_KD, DR_ACTUATOR_KP, DR_ACTUATOR_LATENCY, DR_BASE_FORCE, DR_CHANNELS, DR_DISTRIBUTIONS, DR_GRAVITY, DR_JOINT_DAMPING, DR_MAT_OTHER,
                               DR_MAT_ROBOT, DR_MASS_BODIES, DR_MASS_CHANNELS, DR_MASS_FLOOR, DR_MASS_PLATE, DR_MASS_PLATE_DENSITY, DR_MAX_EFFORT, DR_MAX_VELOCITY, DR_OBS_INTERVAL, DR_OBS_RESET, DR_ON_STARTUP, DR_OPERATIONS, DR_RESET_CHANNELS,
                               DR_RESET_JOINT_POS, DR_RESET_JOINT_VEL, DR_RESET_ORIENTATION, DR_RESET_POSITION, MODE_LOCO, MODE_MANI, NUM_BODIES, DRChannel)
 
@@ -226,6 +235,46 @@ def _least_mass(ch: DRChannel, lo: float, hi: float, nominal: float):
     return nominal + low if ch.operation == DR_OPERATIONS["additive"] else nominal * low if ch.operation == DR_OPERATIONS["scaling"] else low
 
 
+_ACTUATOR = {"joint_kps": DR_ACTUATOR_KP, "joint_kds": DR_ACTUATOR_KD, "command_latency": DR_ACTUATOR_LATENCY}
+
+
+def _actuator_channel(where: str, attribute: str, entry: dict):
+    """One actuator entry (`joint_kps`, `joint_kds`, `command_latency`) -> (trigger, DRChannel): exactly one trigger, a scalar pair."""
+    if entry is None:
+        raise ValueError(f"Randomization parameters for {where} is not provided.")
+    triggers = [t for t in ("on_startup", "on_reset", "on_interval") if t in entry]
+    if len(triggers) != 1:
+        raise NotImplementedError(f"{where}: give exactly one of on_startup, on_reset, on_interval")
+    trigger = triggers[0]
+    e = entry[trigger]
+    need = _ON_INTERVAL_KEYS if trigger == "on_interval" else _ON_RESET_KEYS
+    if e is None or not set(need).issubset(e.keys()):
+        raise ValueError(f"Please ensure the following randomization parameters for {where} {trigger} are provided: " + ", ".join(need) + ".")
+    op, dist = str(e["operation"]), str(e["distribution"])
+    if op not in DR_OPERATIONS or dist not in DR_DISTRIBUTIONS:
+        raise ValueError(f"{where} {trigger}: unsupported operation {op!r} or distribution {dist!r}")
+    if attribute == "command_latency" and op == "scaling":
+        raise ValueError(f"{where} {trigger}: operation 'scaling' is refused: the nominal latency is 0 sub-steps, so a factor changes nothing - use additive or direct")
+    raw = e["distribution_parameters"]
+    try:
+        prm = np.asarray(raw, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{where} {trigger}: distribution_parameters must be numbers, got {raw!r}") from None
+    if prm.shape != (2,):
+        raise ValueError(f"{where} {trigger}: distribution_parameters must be [a, b] (one draw per env, applied to the 12 driven joints), got shape {prm.shape}")
+    if not np.isfinite(prm).all():
+        raise ValueError(f"{where} {trigger}: distribution_parameters must be finite")
+    if DR_DISTRIBUTIONS[dist] == DR_DISTRIBUTIONS["loguniform"] and not (prm > 0).all():
+        raise ValueError(f"{where} {trigger}: loguniform parameters must be positive")
+    interval = {"on_startup": DR_ON_STARTUP, "on_reset": 0}.get(trigger)
+    if interval is None:
+        interval = int(e["frequency_interval"])
+        if interval < 1:
+            raise ValueError(f"{where}: frequency_interval must be >= 1")
+    return trigger, DRChannel(enabled=1, operation=DR_OPERATIONS[op], distribution=DR_DISTRIBUTIONS[dist], interval=interval,
+                              p0=[float(prm[0])] * 3, p1=[float(prm[1])] * 3)
+
+
 class Randomizer:
     def __init__(self, sim_config):
         self._cfg = sim_config.task_config
@@ -244,6 +293,10 @@ class Randomizer:
         self._mass_channels: List[DRChannel] = [DRChannel() for _ in range(DR_MASS_CHANNELS)]
         self._mass_body_p0: List[float] = [0.0] * NUM_BODIES
         self._mass_body_p1: List[float] = [0.0] * NUM_BODIES
+        # actuator channels (EngineParams.dr_actuator): [kp, kd, command latency], one draw per env; checked against each block's actuator
+        # family and gains when the task builds the block (check_actuator)
+        self._actuator_channels: List[DRChannel] = [DRChannel() for _ in range(DR_ACTUATOR_CHANNELS)]
+        self._actuator_where = {}
         self._observations_dr_params = None
         self._actions_dr_params = None
         self.startup_scales = dict()          # (group, view) -> per-env factors drawn by apply_on_startup_domain_randomization
@@ -287,6 +340,8 @@ class Randomizer:
                         continue          # reset-state entries: set_up_domain_randomization refuses every trigger but on_reset, with the reason
                     if attribute == "body_masses" and group == "articulation_views":
                         continue          # a mass channel of the engine (set_up_domain_randomization)
+                    if attribute in _ACTUATOR and group == "articulation_views":
+                        continue          # an actuator channel of the engine (set_up_domain_randomization)
                     if attribute in ("mass", "density") and group == "rigid_prim_views":
                         if view != PLATE_VIEW:
                             raise NotImplementedError(_MASS_REFUSED.format(view=view, attribute=attribute))
@@ -376,6 +431,9 @@ class Randomizer:
                         if attribute == "body_masses":
                             self._set_up_mass(("articulation_views", view, attribute), entry, DR_MASS_BODIES, task)
                             continue
+                        if attribute in _ACTUATOR:
+                            self._set_up_actuator(("articulation_views", view, attribute), entry)
+                            continue
                         if attribute == "joint_friction":          # the joint friction coefficient itself is not modelled: scaling it changes nothing
                             import warnings
                             warnings.warn(f"articulation_views.{view}.joint_friction: joint friction is not modelled by this engine; entry ignored")
@@ -438,6 +496,37 @@ class Randomizer:
             self._mass_body_p0 = [float(lo[k]) for k in order]
             self._mass_body_p1 = [float(hi[k]) for k in order]
         self.active_domain_randomizations[key + (trigger,)] = np.array(entry[trigger]["distribution_parameters"])
+
+    def _set_up_actuator(self, key, entry):
+        """joint_kps / joint_kds / command_latency: one trigger -> the actuator channel of every block (check_actuator scopes it)."""
+        trigger, c = _actuator_channel(".".join(key), key[-1], entry)
+        self._actuator_channels[_ACTUATOR[key[-1]]] = c
+        self._actuator_where[_ACTUATOR[key[-1]]] = ".".join(key)
+        self.active_domain_randomizations[key + (trigger,)] = np.array(entry[trigger]["distribution_parameters"])
+
+    def check_actuator(self, ep):
+        """The actuator entries against the block they reach (called by the task when it builds the block): the actuator family decides which
+        entries exist, and a bounded gain range must stay positive for THIS block's nominal gains."""
+        if not self.randomize:
+            return
+        ckp, ckd, cl = (self._actuator_channels[c] for c in (DR_ACTUATOR_KP, DR_ACTUATOR_KD, DR_ACTUATOR_LATENCY))
+        w = self._actuator_where
+        pd = int(ep.variant) >= 1
+        if ckp.enabled and not pd and int(ep.drive_mode) != 1:
+            raise NotImplementedError(f"{w[DR_ACTUATOR_KP]}: there is no position gain in {'effort' if int(ep.drive_mode) == 2 else 'velocity'} control "
+                                      "(the drive has a velocity gain only: joint_kds); joint_kps exists on the PD-actuator tasks and in position control")
+        if ckd.enabled and not pd and int(ep.drive_mode) == 2:
+            raise NotImplementedError(f"{w[DR_ACTUATOR_KD]}: effort control runs with the drive gains off, so there is no velocity gain to randomise")
+        if cl.enabled and not pd:
+            raise NotImplementedError(f"{w[DR_ACTUATOR_LATENCY]}: the command latency exists on the PD-actuator tasks only (controller variants 1 / 2: "
+                                      "the PD law is re-evaluated every sub-step there); the velocity-drive tasks have none")
+        for c, name, nominal in ((ckp, "joint_kps", float(ep.pd_kp)), (ckd, "joint_kds", float(ep.kd))):
+            if not c.enabled:
+                continue
+            least = _least_mass(c, c.p0[0], c.p1[0], nominal)
+            if least is not None and least <= 0:
+                raise ValueError(f"{w[_ACTUATOR[name]]}: the distribution's range reaches a non-positive gain ({least:g} on a nominal of {nominal:g}); "
+                                 "a gaussian is floored instead, a uniform / loguniform range must stay positive")
 
     @staticmethod
     def _robot_model(task):
@@ -509,7 +598,8 @@ class Randomizer:
             mass[DR_MASS_PLATE] = DRChannel(); mass[DR_MASS_PLATE_DENSITY] = DRChannel()
         return dict(dr_enabled=1, dr_min_frequency=int(self.min_frequency), dr=list(self._channels), dr_mat=mat, dr_mat_buckets=buckets,
                     dr_reset=list(self._reset_channels[MODE_MANI if mode == MODE_MANI else MODE_LOCO]),
-                    dr_mass=mass, dr_mass_body_p0=list(self._mass_body_p0), dr_mass_body_p1=list(self._mass_body_p1))
+                    dr_mass=mass, dr_mass_body_p0=list(self._mass_body_p0), dr_mass_body_p1=list(self._mass_body_p1),
+                    dr_actuator=list(self._actuator_channels))
 
     # The wrapper calls these two exactly where the reference does (vec_env_rlgames.py:56-58,70-72).  The noise has already been /
     # will be applied inside lm_step with the reference's counter semantics (randomize.py:212-306), so they hand the tensor through.

@@ -3,7 +3,10 @@ the contact-material channel adds to k_step_dr (the same block + the feet's mate
 the four reset-state channels add (the same block + joint_positions / joint_velocities / position / orientation at the reference's amplitudes,
 min_frequency 0: every reset draws; and behind the YAML's min_frequency, which outlasts the run: no reset draws), and what the mass channels add
 (the same block + body_masses drawn once per env / redrawn every step; on QuadrupedManipulatePlate the same pair for the plate's mass, against that
-task's own randomised leg).  `resets_per_step` is the mean number of envs reset per timed step of each leg."""
+task's own randomised leg), and what the actuator channels add (joint_kps + joint_kds + command_latency on QuadrupedPoseControlCustomController,
+drawn once per env / redrawn every step, against that task's own randomised leg; joint_kds alone on QuadrupedPoseControl).  Leg names given on
+the command line restrict the run to those legs (ratios are printed for the pairs that ran).  `resets_per_step` is the mean number of envs
+reset per timed step of each leg."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -20,6 +23,12 @@ BODY_MASSES = lambda e: {"articulation_views": {"robot_view": {"body_masses": e}
 PLATE_MASS = lambda e: {"rigid_prim_views": {"plate": {"mass": e}}}
 _DR = lambda prm=None, **kw: {"task": {"domain_randomization": dict(randomize=True, **({"randomization_params": prm} if prm else {}), **kw)}}
 MANI = "QuadrupedManipulatePlate"
+CC = "QuadrupedPoseControlCustomController"
+_G = lambda trigger, **kw: {trigger: dict(operation="scaling", distribution="loguniform", distribution_parameters=[0.5, 2.0], **kw)}
+_L = lambda trigger, **kw: {trigger: dict(operation="direct", distribution="uniform", distribution_parameters=[0.0, 6.0], **kw)}
+ACTUATOR = lambda t, **kw: {"articulation_views": {"robot_view": {"joint_kps": _G(t, **kw), "joint_kds": _G(t, **kw), "command_latency": _L(t, **kw)}}}
+JOINT_KDS = lambda e: {"articulation_views": {"robot_view": {"joint_kds": e}}}
+only = set(sys.argv[1:])
 resets = {}
 for name, ov in (("plain", None), ("randomised", {"task": {"domain_randomization": {"randomize": True}}}),
                  ("randomised_material", {"task": {"domain_randomization": {"randomize": True, "randomization_params": MATERIAL}}}),
@@ -31,19 +40,27 @@ for name, ov in (("plain", None), ("randomised", {"task": {"domain_randomization
                  ("randomised_body_masses_startup", _DR(BODY_MASSES(_M("on_startup")))),
                  ("randomised_body_masses_every_step", _DR(BODY_MASSES(_M("on_interval", frequency_interval=1)))),
                  ("mani_randomised", _DR()), ("mani_randomised_plate_mass_startup", _DR(PLATE_MASS(_M("on_startup")))),
-                 ("mani_randomised_plate_mass_every_step", _DR(PLATE_MASS(_M("on_interval", frequency_interval=1))))):
-    env = lm.make_env(MANI if name.startswith("mani_") else "QuadrupedPoseControl", num_envs=4096, overrides=ov)
+                 ("mani_randomised_plate_mass_every_step", _DR(PLATE_MASS(_M("on_interval", frequency_interval=1)))),
+                 # actuator channels: kp + kd + command latency on the custom-controller task (its own randomised leg: the YAML's block is empty,
+                 # an empty joint_friction entry switches the randomised kernel on), and the velocity gain alone on the velocity drive
+                 ("cc_randomised", _DR({"articulation_views": {"robot_view": {"joint_friction": {}}}})),
+                 ("cc_randomised_actuator_startup", _DR(ACTUATOR("on_startup"))),
+                 ("cc_randomised_actuator_every_step", _DR(ACTUATOR("on_interval", frequency_interval=1))),
+                 ("randomised_joint_kds_every_step", _DR(JOINT_KDS(_G("on_interval", frequency_interval=1))))):
+    if only and name not in only:
+        continue
+    env = lm.make_env(MANI if name.startswith("mani_") else CC if name.startswith("cc_") else "QuadrupedPoseControl", num_envs=4096, overrides=ov)
     e = env._task.engine; N = 4096
     g = torch.Generator(device="cuda").manual_seed(0)
     pool = [torch.rand(N, 12, device="cuda", generator=g) * 2 - 1 for _ in range(16)]
-    o = (torch.empty(N, 64, device="cuda"), torch.empty(N, 93, device="cuda"), torch.empty(N, device="cuda"), torch.empty(N, dtype=torch.int64, device="cuda"), torch.empty(13, device="cuda"))
+    o = (torch.empty(N, e.num_obs, device="cuda"), torch.empty(N, 93, device="cuda"), torch.empty(N, device="cuda"), torch.empty(N, dtype=torch.int64, device="cuda"), torch.empty(13, device="cuda"))
     for t in range(50): e.step(pool[t % 16], None, *o)
     torch.cuda.synchronize(); ep0 = int(e.cnt[5].sum().item()); t0 = time.perf_counter()
     for t in range(500): e.step(pool[t % 16], None, *o)
     torch.cuda.synchronize(); res[name] = (time.perf_counter() - t0) / 500 * 1e6
     resets[name] = (int(e.cnt[5].sum().item()) - ep0) / 500
     env.close()
-ratio = lambda a, b: res[a] / res[b] - 1
+ratio = lambda a, b: res[a] / res[b] - 1 if a in res and b in res else None
 print(json.dumps({"us_per_step": res, "overhead": ratio("randomised", "plain"),
                   "material_overhead_on_k_step_dr": ratio("randomised_material", "randomised"),
                   "reset_state_overhead_on_k_step_dr": ratio("randomised_reset_state", "randomised_min_frequency_0"),
@@ -52,4 +69,7 @@ print(json.dumps({"us_per_step": res, "overhead": ratio("randomised", "plain"),
                   "body_masses_every_step_overhead_on_k_step_dr": ratio("randomised_body_masses_every_step", "randomised"),
                   "plate_mass_startup_overhead_on_k_step_dr": ratio("mani_randomised_plate_mass_startup", "mani_randomised"),
                   "plate_mass_every_step_overhead_on_k_step_dr": ratio("mani_randomised_plate_mass_every_step", "mani_randomised"),
+                  "actuator_startup_overhead_on_k_step_dr_pd": ratio("cc_randomised_actuator_startup", "cc_randomised"),
+                  "actuator_every_step_overhead_on_k_step_dr_pd": ratio("cc_randomised_actuator_every_step", "cc_randomised"),
+                  "joint_kds_every_step_overhead_on_k_step_dr": ratio("randomised_joint_kds_every_step", "randomised"),
                   "resets_per_step": resets}))
