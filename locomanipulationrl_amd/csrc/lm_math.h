@@ -6,7 +6,7 @@
 // packed fp32 instructions of gfx90a+ (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: two fp32 results per lane per issue slot, the rate the
 // 157 TFLOP/s vector peak is quoted at), and a plain float used as an operand of a packed op is broadcast by the instruction's op_sel bits,
 // without a move.  The step kernel uses the pair to run the two structurally identical chains of a limb
-// (shell -> link4 -> link3 and shell -> link1 -> link2) in the same instructions (lm_engine.hip, limb_kinematics / limb_dynamics).
+// (shell -> link4 -> link3 and shell -> link1 -> link2) in the same instructions (lm_dynamics.h, limb_kinematics / limb_dynamics).
 #pragma once
 #include <hip/hip_runtime.h>
 

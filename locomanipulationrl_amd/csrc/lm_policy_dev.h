@@ -102,7 +102,7 @@ __shared__ unsigned long long lm_gnn_stamp_lds[4][16];      // diagnostic builds
 #define MLP_STAMP(k) do { } while (0)
 #endif
 
-// ---- counter-based standard normal for the fused action sampling (same generator as lm_engine.hip dr_sample, stream 9)
+// ---- counter-based standard normal for the fused action sampling (same generator as lm_samplers.h dr_sample, stream 9)
 __device__ __forceinline__ float ro_normal(uint32_t seed, uint32_t env, uint32_t key, uint32_t idx) {
   // actions 2p and 2p+1 are the cosine and sine branches of one Box-Muller pair
   float u1, u2; lm_rng_pair(lm_rng_base(seed, LM_RNG_STREAM_ACTION_SAMPLING, env, key), idx >> 1, &u1, &u2);

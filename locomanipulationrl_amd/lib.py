@@ -52,12 +52,17 @@ def _fill_channel(dst, ch):
         dst.p0[c] = float(ch.p0[c]); dst.p1[c] = float(ch.p1[c])
 
 
-def make_reset_dr(ep) -> LmResetDr:
-    """EngineParams.dr_reset -> C struct (all channels off for a block that carries none)."""
-    r = LmResetDr()
-    for i, ch in enumerate(getattr(ep, "dr_reset", None) or []):
+def _make_dr(struct, ep, attr):
+    """The channel list EngineParams.<attr> -> a fresh C struct of a setter family (all channels off for a block that carries none)."""
+    r = struct()
+    for i, ch in enumerate(getattr(ep, attr, None) or []):
         _fill_channel(r.ch[i], ch)
     return r
+
+
+def make_reset_dr(ep) -> LmResetDr:
+    """EngineParams.dr_reset -> C struct (all channels off for a block that carries none)."""
+    return _make_dr(LmResetDr, ep, "dr_reset")
 
 
 class LmMassDr(C.Structure):
@@ -68,9 +73,7 @@ class LmMassDr(C.Structure):
 
 def make_mass_dr(ep) -> LmMassDr:
     """EngineParams.dr_mass / dr_mass_body_p0 / dr_mass_body_p1 -> C struct (all channels off for a block that carries none)."""
-    r = LmMassDr()
-    for i, ch in enumerate(getattr(ep, "dr_mass", None) or []):
-        _fill_channel(r.ch[i], ch)
+    r = _make_dr(LmMassDr, ep, "dr_mass")
     for dst, name in ((r.body_p0, "dr_mass_body_p0"), (r.body_p1, "dr_mass_body_p1")):
         vals = list(getattr(ep, name, None) or [])
         if vals and len(vals) != NUM_BODIES:
@@ -87,10 +90,12 @@ class LmActuatorDr(C.Structure):
 
 def make_actuator_dr(ep) -> LmActuatorDr:
     """EngineParams.dr_actuator -> C struct (all channels off for a block that carries none)."""
-    r = LmActuatorDr()
-    for i, ch in enumerate(getattr(ep, "dr_actuator", None) or []):
-        _fill_channel(r.ch[i], ch)
-    return r
+    return _make_dr(LmActuatorDr, ep, "dr_actuator")
+
+
+# the setter families of the domain randomisation (DESIGN.md 3.6): EngineParams attribute, maker of the C struct, C entry point
+_DR_FAMILIES = (("dr_reset", make_reset_dr, "lm_set_reset_randomization"), ("dr_mass", make_mass_dr, "lm_set_mass_randomization"),
+                ("dr_actuator", make_actuator_dr, "lm_set_actuator_randomization"))
 
 
 ABI_VERSION = 5          # LM_ABI_VERSION of include/lm_engine.h this mirror was written against
@@ -188,9 +193,7 @@ def hipcc_command(extra, out):
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
-    """Compile csrc/lm_engine.hip for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    src = os.path.join(_CSRC, "lm_engine.hip")
-    src2 = os.path.join(_CSRC, "lm_policy.hip")
+    """Compile the engine (csrc/*.hip) for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     inc = os.path.join(os.path.dirname(os.path.dirname(_CSRC)), "include")
     import glob
     deps = sorted(glob.glob(os.path.join(_CSRC, "*.hip")) + glob.glob(os.path.join(_CSRC, "*.h")) + glob.glob(os.path.join(inc, "*.h")))      # every source the .so is built from
@@ -285,19 +288,12 @@ class Engine:
             rc = self.lib.lm_create(C.byref(self._h), self.num_envs, table.ctypes.data_as(C.c_void_p), arr, len(params),
                                     int(split_env or 0), C.c_uint32(seed))
         self._check(rc)
-        for b, ep in enumerate(params):          # reset-state channels: handed over per block, before the first step
-            if any(ch.enabled for ch in (getattr(ep, "dr_reset", None) or [])):
-                rd = make_reset_dr(ep)
-                with torch.cuda.device(self.device):
-                    self._check(self.lib.lm_set_reset_randomization(self._h, b, C.byref(rd)))
-            if any(ch.enabled for ch in (getattr(ep, "dr_mass", None) or [])):          # mass channels: the same way
-                md = make_mass_dr(ep)
-                with torch.cuda.device(self.device):
-                    self._check(self.lib.lm_set_mass_randomization(self._h, b, C.byref(md)))
-            if any(ch.enabled for ch in (getattr(ep, "dr_actuator", None) or [])):          # actuator channels: the same way
-                ad = make_actuator_dr(ep)
-                with torch.cuda.device(self.device):
-                    self._check(self.lib.lm_set_actuator_randomization(self._h, b, C.byref(ad)))
+        for b, ep in enumerate(params):          # reset-state, mass and actuator channels: handed over per block, before the first step
+            for attr, make, setter in _DR_FAMILIES:
+                if any(ch.enabled for ch in (getattr(ep, attr, None) or [])):
+                    dr = make(ep)
+                    with torch.cuda.device(self.device):
+                        self._check(getattr(self.lib, setter)(self._h, b, C.byref(dr)))
         self.seed = int(seed) & 0xFFFFFFFF
         N = self.num_envs
         self.state = self._wrap(PTR_STATE, (STATE_ROWS, N), "<f4")
@@ -338,28 +334,27 @@ class Engine:
     def terms(self):
         return self._view(PTR_TERMS, (TERM_ROWS, self.num_envs))
 
+    def _record(self, name, kind, rows, missing):
+        """float [rows][N] view of a record that exists only on engines that asked for it (lm_ptr gives NULL otherwise: EngineError(missing))."""
+        if name not in self._views:
+            ptr = self.lib.lm_ptr(self._h, kind)
+            if not ptr:
+                raise EngineError(missing)
+            self._views[name] = self.torch.as_tensor(_DevArray(ptr, (rows, self.num_envs), "<f4", self), device=self.device)
+        return self._views[name]
+
     @property
     def dr_reset_state(self):
         """float [31][N]: the state each env was last reset to by step() - q 12, qd 12, free-body position 3, quaternion (w, x, y, z) 4 -
         nominal resets included.  Randomised engines only (dr_enabled)."""
-        if "dr_reset_state" not in self._views:
-            ptr = self.lib.lm_ptr(self._h, PTR_DR_RESET_STATE)
-            if not ptr:
-                raise EngineError("dr_reset_state: the engine was created without dr_enabled (no reset-state record)")
-            self._views["dr_reset_state"] = self.torch.as_tensor(_DevArray(ptr, (DR_RESET_ROWS, self.num_envs), "<f4", self), device=self.device)
-        return self._views["dr_reset_state"]
+        return self._record("dr_reset_state", PTR_DR_RESET_STATE, DR_RESET_ROWS, "dr_reset_state: the engine was created without dr_enabled (no reset-state record)")
 
     @property
     def dr_mass(self):
         """float [23][N]: the masses the last step used, floored - row 0 the plate's mass, row 1 the factor on its inertia about the COM,
         rows 2..22 the 21 body masses in table order (RobotModel.table_body_order()).  The nominal values until a mass channel draws.
         Randomised engines only (dr_enabled)."""
-        if "dr_mass" not in self._views:
-            ptr = self.lib.lm_ptr(self._h, PTR_DR_MASS)
-            if not ptr:
-                raise EngineError("dr_mass: the engine was created without dr_enabled (no mass record)")
-            self._views["dr_mass"] = self.torch.as_tensor(_DevArray(ptr, (DR_MASS_ROWS, self.num_envs), "<f4", self), device=self.device)
-        return self._views["dr_mass"]
+        return self._record("dr_mass", PTR_DR_MASS, DR_MASS_ROWS, "dr_mass: the engine was created without dr_enabled (no mass record)")
 
     @property
     def dr_plate_mass(self):
@@ -380,13 +375,8 @@ class Engine:
             self._check(self.lib.lm_enable_contact_forces(self._h, 1 if on else 0))
 
     def _contact_record(self):
-        if "contact" not in self._views:
-            ptr = self.lib.lm_ptr(self._h, PTR_CONTACT)
-            if not ptr:
-                raise EngineError("contact forces are not reported by this engine: call enable_contact_forces() first "
-                                  "(task YAML: sim.engine.contact_forces: true)")
-            self._views["contact"] = self.torch.as_tensor(_DevArray(ptr, (CONTACT_ROWS, self.num_envs), "<f4", self), device=self.device)
-        return self._views["contact"]
+        return self._record("contact", PTR_CONTACT, CONTACT_ROWS, "contact forces are not reported by this engine: call enable_contact_forces() first "
+                            "(task YAML: sim.engine.contact_forces: true)")
 
     @property
     def contact_forces(self):
@@ -403,12 +393,7 @@ class Engine:
     def dr_actuator(self):
         """float [3][N]: what the last step used - row 0 the position gain kp, row 1 the velocity gain kd (both floored), row 2 the command
         latency d in sub-steps.  The nominal values (pd_kp, kd, 0) until an actuator channel draws.  Randomised engines only (dr_enabled)."""
-        if "dr_actuator" not in self._views:
-            ptr = self.lib.lm_ptr(self._h, PTR_DR_ACTUATOR)
-            if not ptr:
-                raise EngineError("dr_actuator: the engine was created without dr_enabled (no actuator record)")
-            self._views["dr_actuator"] = self.torch.as_tensor(_DevArray(ptr, (DR_ACTUATOR_ROWS, self.num_envs), "<f4", self), device=self.device)
-        return self._views["dr_actuator"]
+        return self._record("dr_actuator", PTR_DR_ACTUATOR, DR_ACTUATOR_ROWS, "dr_actuator: the engine was created without dr_enabled (no actuator record)")
 
     @property
     def dr_kp(self):
