@@ -75,6 +75,46 @@ int lm_rollout_create(lm_rollout** out, struct lm_engine* env, int policy, const
 int lm_rollout_run(lm_rollout* r, int use_graph, void* stream);
 int lm_rollout_destroy(lm_rollout* r);
 
+/* ---- evaluation: mean actions and episode records (what the reference's scripts do with eval = True: agent.set_mode('eval') and the
+ * trainer's evaluation loop).  Both are switches of a plan, off after lm_rollout_create; a plan that uses neither runs the kernels and
+ * writes the bits it did before they existed.  Flipping one invalidates a captured graph as lm_set_seed does (re-captured on the next
+ * run, never refused).  All three return 0 or LM_EINVAL (-1): a null plan / handle, a calling thread whose current device is not the
+ * engine's, and lm_episode_update with a null rewards, dones or record.
+ *
+ * Deterministic mode (on != 0): actions[t] = the forward's mean, bit for bit (the mean itself, not mean + exp(log_std) * 0, so an
+ * overflowing exp(log_std) cannot make a NaN); logp[t] = the stochastic expression at eps = 0, sum_j (-log_std_j - ln sqrt(2 pi)) in the
+ * same summation order (groups of four, then (p0 + p1) + (p2 + 0)); no normal is drawn and noise_seed is not read.  Values, observations,
+ * rewards, dones and extras are written as always.  lm_sample_actions belongs to no plan and always samples. */
+int lm_rollout_set_deterministic(lm_rollout* r, int on);
+
+/* Episode record: a caller-owned device buffer float [LM_EPISODE_ROWS][N] that the caller zeroes to start a measurement and that persists
+ * across runs (episodes cross rollout boundaries).  Rows, per env:
+ *   0 running return | 1 running length | 2 episodes completed | 3 sum of the returns of completed episodes | 4 sum of their lengths |
+ *   5 ended by goal | 6 ended by timeout | 7 ended by failure | 8 return of the last completed episode
+ * After step t of env e, with r = rewards[t][e], d = dones[t][e], g = the env's goal_reset_buf after that step and M = max_episode of
+ * the env's parameter block (the two blocks of a co-training engine may differ):
+ *   if (cap > 0 && row2 >= cap) skip the env;          the first `cap` episodes of EVERY env: no bias towards short episodes
+ *   row0 = row0 + r;  row1 = row1 + 1;                 plain fp32 adds, in step order
+ *   if (d) { row2 += 1; row3 = row3 + row0; row4 = row4 + row1;  g ? row5 += 1 : (row1 >= M - 1 ? row6 += 1 : row7 += 1);
+ *            row8 = row0; row0 = 0; row1 = 0; }
+ * A length counts the step that resets the env, as progress_buf does: zero the record when every env is about to reset (lm_reset_all), or
+ * the first episode of an env is seen shorter than it was and its timeout is counted as a failure.
+ * The reward of a step belongs to the episode that step ends (the env is reset at the start of the next step).  A failure on the very step
+ * the timeout would fire counts as a timeout.  The outcome is read from the flags, never from the reward (fall_pen is 0.0 in the shipped
+ * tasks).  Counts and lengths are floats: exact below 2^24.  record == NULL switches recording off; episode_cap <= 0 means no cap.
+ * Enqueue, graph and persistent runs fill identical buffers and identical records.  The persistent kernels with either switch on are builds
+ * of their own.  A recording build is shipped only where it compiles with 0 bytes of scratch memory: the MLP on 64-wide observations.  For
+ * the MLP on 88-wide observations and for the GNN, LM_ROLLOUT_PERSISTENT returns -1 for a plan with a record attached and LM_ROLLOUT_AUTO
+ * takes the graph; deterministic mode alone runs persistent for every policy.  Randomised engines and engines with contact reporting on
+ * keep their rule (graph / enqueue only). */
+#define LM_EPISODE_ROWS 9
+int lm_rollout_set_episode_record(lm_rollout* r, float* record, int episode_cap);
+
+/* The same update as one small launch, for callers that step with lm_step themselves: rewards [N] and dones int64 [N] as lm_step wrote
+ * them for the step that has just been enqueued on `stream`; g and M are read from the engine.  The enqueue and graph rollouts call it
+ * after each lm_step. */
+int lm_episode_update(struct lm_engine* h, const float* rewards, const int64_t* dones, float* record, int episode_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ extern "C" void lm_dbg_pass2_read(unsigned int* out, int clear) {
 #include "lm_policy_dev.h"
 #include "lm_internal.h"
 #include "lm_step.h"      // the device code of the step: lm_samplers.h, lm_dynamics.h, lm_task.h, lm_step.h
+#include "lm_rollout_dev.h"      // RolloutDev, step_dispatch, PolicySmem: shared with the evaluation builds (lm_engine_ev.hip)
 
 // The step kernels.  One launch per step(); a wavefront picks its specialisation (task mode x actuator family) from the kernel arguments.  The
 // velocity-drive tasks (k_step: the headline) and the PD-actuator families (k_step_pd) are separate kernels, so that the register allocation
@@ -104,22 +105,6 @@ __global__ void __launch_bounds__(64) k_step_dr_pd_cf(StepArgs A) {
 // never wait for each other, so a step costs a block its own time rather than the slowest block's, and no launch boundary is paid.
 // The per-step reductions go to per-step accumulators (blocks drift apart); k_rollout_finalize publishes the extras afterwards, in
 // step order, with the same arithmetic as the last-arriver path of write_outputs.
-struct RolloutDev {
-  const float* params; const float* log_std;
-  float *obs, *actions, *logp, *values, *rewards; int64_t* dones;
-  long long* acc_steps; int T; uint32_t noise_seed;
-};
-
-// the step of the persistent kernel as a real call: its ~350 registers are then allocated separately from the policy tile's
-LM_DEV void step_dispatch(const StepArgs& B, const lm_params* P, float* sTab, float* sObs, float* sSt, float4* sStash) {
-  if (P->variant == 0) { if (P->mode == LM_MODE_LOCO) step_body<0, 0, 0, 1>(B, P, sTab, sObs, sSt, sStash); else step_body<1, 0, 0, 1>(B, P, sTab, sObs, sSt, sStash); }
-  else if (P->variant == 1) { if (P->mode == LM_MODE_LOCO) step_body<0, 1, 0, 1>(B, P, sTab, sObs, sSt, sStash); else step_body<1, 1, 0, 1>(B, P, sTab, sObs, sSt, sStash); }
-  else { if (P->mode == LM_MODE_LOCO) step_body<0, 2, 0, 1>(B, P, sTab, sObs, sSt, sStash); else step_body<1, 2, 0, 1>(B, P, sTab, sObs, sSt, sStash); }
-}
-
-template <int NOBS, int POLICY> struct PolicySmem { MlpSmem<NOBS> M; };
-template <int NOBS> struct PolicySmem<NOBS, LM_POLICY_GNN> { GnnSmem M; };
-
 template <int NOBS, int POLICY>
 __global__ void __launch_bounds__(256) k_rollout(StepArgs A, RolloutDev R) {
   __shared__ __attribute__((aligned(16))) float sTab[LM_ITAB_FLOATS + 2];
@@ -969,7 +954,13 @@ int lm_internal_rollout(lm_engine* h, int policy, const LmRolloutArgs& R, hipStr
   RolloutDev D; D.params = R.params; D.log_std = R.log_std; D.obs = R.obs; D.actions = R.actions; D.logp = R.logp; D.values = R.values;
   D.rewards = R.rewards; D.dones = R.dones; D.acc_steps = R.acc_steps; D.T = R.T; D.noise_seed = R.noise_seed;
   static const bool streaming = getenv("LM_ROLLOUT_STREAMING_MLP") != nullptr;      // kernel experiments: the four-wavefront tile with streamed weights
-  if (policy == LM_POLICY_MLP && R.nobs == 64 && !streaming) hipLaunchKernelGGL(k_rollout_mlp<64>, dim3(h->nblocks), dim3(256), 0, s, A, D);
+  const int ev = (R.deterministic ? LM_EV_DET : 0) | (R.record ? LM_EV_REC : 0);
+  if (ev) {      // evaluation builds (lm_engine_ev.hip; the MLP always on the resident tile)
+    if (R.record && !lm_internal_rollout_records(policy, R.nobs)) return fail(-1, "persistent rollout: no recording build for this policy / observation width; recording plans run through the graph mode");
+    RolloutEv E; E.record = R.record; E.cap = R.episode_cap;
+    if (lm_internal_launch_rollout_ev(&A, &D, &E, ev, policy, R.nobs, h->nblocks, s)) return -1;
+  }
+  else if (policy == LM_POLICY_MLP && R.nobs == 64 && !streaming) hipLaunchKernelGGL(k_rollout_mlp<64>, dim3(h->nblocks), dim3(256), 0, s, A, D);
   else if (policy == LM_POLICY_MLP && R.nobs == LM_MAX_OBS && !streaming) hipLaunchKernelGGL(k_rollout_mlp<LM_MAX_OBS>, dim3(h->nblocks), dim3(256), 0, s, A, D);
   else if (policy == LM_POLICY_MLP && R.nobs == 64) hipLaunchKernelGGL((k_rollout<64, LM_POLICY_MLP>), dim3(h->nblocks), dim3(256), 0, s, A, D);
   else if (policy == LM_POLICY_MLP && R.nobs == LM_MAX_OBS) hipLaunchKernelGGL((k_rollout<LM_MAX_OBS, LM_POLICY_MLP>), dim3(h->nblocks), dim3(256), 0, s, A, D);
@@ -982,6 +973,15 @@ int lm_internal_rollout(lm_engine* h, int policy, const LmRolloutArgs& R, hipStr
 int lm_internal_rollout_supported(const lm_engine* h, int policy, int nobs) {
   if (!h || h->dr_enabled || h->contact_on || nobs != h->num_obs) return 0;
   return (policy == LM_POLICY_MLP && (nobs == 64 || nobs == LM_MAX_OBS)) || (policy == LM_POLICY_GNN && nobs == 64);
+}
+
+// Recording builds of the persistent kernels exist only where they compile without scratch memory: the resident MLP tile on 64-wide
+// observations.  (With the record, the 88-wide MLP build needs 116 - 156 bytes of scratch per lane against 60 - 72 without and the GNN build
+// 268 - 292 against 236 - 240: not shipped; those plans record in the graph mode.)
+int lm_internal_rollout_records(int policy, int nobs) { return policy == LM_POLICY_MLP && nobs == 64; }
+int lm_internal_on_device(const lm_engine* h) { return h && on_device(h); }
+void lm_internal_episode_info(const lm_engine* h, int* split, int* max_episode) {
+  *split = h->split; max_episode[0] = h->h_params[0].max_episode; max_episode[1] = h->h_params[h->n_tasks == 2 ? 1 : 0].max_episode;
 }
 
 uint64_t lm_internal_args_key(const lm_engine* h) {

@@ -11,6 +11,8 @@ struct LmRolloutArgs {
   float *obs, *actions, *logp, *values, *rewards, *extras; int64_t* dones;
   long long* acc_steps;        // [T][16] int64 accumulators, zero on entry; left zero
   int T, nobs; uint32_t noise_seed;
+  int deterministic;           // lm_rollout_set_deterministic: the *_ev instantiations with the mean-action epilogue
+  float* record; int episode_cap;      // lm_rollout_set_episode_record (record may be null: no recording)
 };
 
 // T x (policy forward -> sampling -> step) + the bootstrap forward in ONE kernel launch (lm_engine.hip); policy = LM_POLICY_MLP / _GNN.
@@ -18,6 +20,12 @@ struct LmRolloutArgs {
 int lm_internal_rollout(lm_engine* h, int policy, const LmRolloutArgs& R, hipStream_t s);
 // 1 when lm_internal_rollout can run this engine / policy / observation width
 int lm_internal_rollout_supported(const lm_engine* h, int policy, int nobs);
+// 1 when the persistent kernel has a build that keeps the episode record for this policy / observation width (else recording plans take the graph)
+int lm_internal_rollout_records(int policy, int nobs);
+// 1 when the calling thread's current device is the engine's
+int lm_internal_on_device(const lm_engine* h);
+// what the episode record needs of the engine: first env of the second parameter block (N when there is one block) and max_episode of both
+void lm_internal_episode_info(const lm_engine* h, int* split, int* max_episode);
 // what a captured lm_step launch has baked into its kernel arguments and the engine may change afterwards: the goal / domain-randomisation seed
 // (lm_set_seed) and which of the unclipped views are kept current (lm_ptr).  A hipGraph captured under another key is re-captured.
 uint64_t lm_internal_args_key(const lm_engine* h);

@@ -61,10 +61,34 @@ __global__ void __launch_bounds__(256) k_mlp_forward(const float* __restrict__ o
 #endif
 }
 
+// The same two forwards with the mean-action epilogue of deterministic plans (lm_rollout_set_deterministic): kernels of their own, so that the
+// sampling forwards above are the code they were.
+__global__ void __launch_bounds__(256) k_gnn_forward_det(const float* __restrict__ obs, int B, const float* __restrict__ W,
+                                                         float* __restrict__ mean, float* __restrict__ value, SampleArgs SA) {
+  __shared__ GnnSmem G;
+  gnn_block<false, true>(obs, 0.f, B, blockIdx.x * GNN_SAMPLES, W, mean, value, SA, G, threadIdx.x);
+}
+template <int NOBS>
+__global__ void __launch_bounds__(256) k_mlp_forward_det(const float* __restrict__ obs, int B, const float* __restrict__ W,
+                                                         float* __restrict__ mean, float* __restrict__ value, SampleArgs SA) {
+  __shared__ MlpSmem<NOBS> M;
+  mlp_block<NOBS, false, true>(obs, 0.f, B, blockIdx.x * 16, W, mean, value, SA, M, threadIdx.x);
+}
+
+// episode record of one step for callers that step with lm_step themselves (and the enqueue / graph rollouts): one lane per env
+__global__ void __launch_bounds__(256) k_episode_update(const float* __restrict__ rewards, const int64_t* __restrict__ dones, const int64_t* __restrict__ cnt,
+                                                        int N, int split, int M0, int M1, float* __restrict__ record, int cap) {
+  const int env = blockIdx.x * blockDim.x + threadIdx.x;
+  if (env >= N) return;
+  episode_update(record, (size_t)N, (size_t)env, rewards[env], dones[env] != 0, cnt[2 * (size_t)N + env] != 0, env >= split ? M1 : M0, cap);
+}
+
 extern "C" {
 
-static int mlp_launch(const float* obs, int batch, int num_obs, const float* params, float* mean, float* value, const SampleArgs& SA, hipStream_t s) {
-  if (num_obs == 64) hipLaunchKernelGGL(k_mlp_forward<64>, dim3((batch + 15) / 16), dim3(256), 0, s, obs, batch, params, mean, value, SA);
+static int mlp_launch(const float* obs, int batch, int num_obs, const float* params, float* mean, float* value, const SampleArgs& SA, hipStream_t s, bool det = false) {
+  if (det && num_obs == 64) hipLaunchKernelGGL(k_mlp_forward_det<64>, dim3((batch + 15) / 16), dim3(256), 0, s, obs, batch, params, mean, value, SA);
+  else if (det && num_obs == 88) hipLaunchKernelGGL(k_mlp_forward_det<88>, dim3((batch + 15) / 16), dim3(256), 0, s, obs, batch, params, mean, value, SA);
+  else if (num_obs == 64) hipLaunchKernelGGL(k_mlp_forward<64>, dim3((batch + 15) / 16), dim3(256), 0, s, obs, batch, params, mean, value, SA);
   else if (num_obs == 88) hipLaunchKernelGGL(k_mlp_forward<88>, dim3((batch + 15) / 16), dim3(256), 0, s, obs, batch, params, mean, value, SA);
   else return -1;
   return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -117,6 +141,8 @@ struct lm_rollout {
   int n_cu; bool persistent_ok;                                   // compute units of the device; engine can run the persistent kernel
   hipGraphExec_t exec; hipStream_t exec_stream;
   uint64_t exec_env_key;                                          // engine seed + requested views baked into the captured kernel arguments
+  bool det; float* record; int cap;                               // lm_rollout_set_deterministic / lm_rollout_set_episode_record
+  bool exec_det; float* exec_record; int exec_cap;                // ... as they were when the graph was captured
 };
 
 static int rollout_enqueue(lm_rollout* r, hipStream_t s) {
@@ -127,14 +153,16 @@ static int rollout_enqueue(lm_rollout* r, hipStream_t s) {
     int rc = 0;
     SampleArgs SA{};       // sampling fused into the forward's epilogue
     if (t < r->T) { SA.log_std = r->log_std; SA.cnt = r->cnt; SA.seed = r->seed; SA.actions = act; SA.logp = r->logp + (size_t)t * N; }
-    if (r->policy == LM_POLICY_MLP) { int rcm = mlp_launch(ob, r->N, r->nobs, r->params, r->mean_tmp, r->values + (size_t)t * N, SA, s); if (rcm) return rcm; }
+    const bool det = r->det && t < r->T;                           // (the bootstrap forward samples nothing)
+    if (r->policy == LM_POLICY_MLP) { int rcm = mlp_launch(ob, r->N, r->nobs, r->params, r->mean_tmp, r->values + (size_t)t * N, SA, s, det); if (rcm) return rcm; }
     else
-      hipLaunchKernelGGL(k_gnn_forward, dim3((r->N + GNN_SAMPLES - 1) / GNN_SAMPLES), dim3(256), 0, s, ob, r->N, r->params, r->mean_tmp, r->values + (size_t)t * N, SA);
+      hipLaunchKernelGGL(det ? k_gnn_forward_det : k_gnn_forward, dim3((r->N + GNN_SAMPLES - 1) / GNN_SAMPLES), dim3(256), 0, s, ob, r->N, r->params, r->mean_tmp, r->values + (size_t)t * N, SA);
     if (rc) return rc;
     if (t == r->T) break;                                        // the last forward only bootstraps the value
     rc = lm_step(r->env, act, nullptr, r->obs + (size_t)(t + 1) * N * r->nobs, nullptr, r->rewards + (size_t)t * N, r->dones + (size_t)t * N,
                  r->extras ? r->extras + (size_t)t * LM_NUM_EXTRAS : nullptr, s);
     if (rc) return rc;
+    if (r->record) { rc = lm_episode_update(r->env, r->rewards + (size_t)t * N, r->dones + (size_t)t * N, r->record, r->cap, s); if (rc) return rc; }
   }
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -157,6 +185,7 @@ int lm_rollout_create(lm_rollout** out, lm_engine* env, int policy, const float*
   r->env = env; r->policy = policy; r->T = T; r->N = lm_num_envs(env); r->nobs = nobs; r->seed = noise_seed;
   r->params = policy_params; r->log_std = log_std; r->obs = obs; r->actions = actions; r->logp = logp; r->values = values;
   r->rewards = rewards; r->dones = dones; r->extras = extras; r->exec = nullptr; r->exec_stream = nullptr;
+  r->det = false; r->record = nullptr; r->cap = 0;
   r->cnt = (const int64_t*)lm_ptr(env, LM_PTR_CNT);
   if (hipMalloc((void**)&r->mean_tmp, (size_t)r->N * 12 * sizeof(float)) != hipSuccess) { delete r; return lm_internal_fail(-2, "lm_rollout_create: hipMalloc failed"); }
   r->acc_steps = nullptr;
@@ -168,24 +197,51 @@ int lm_rollout_create(lm_rollout** out, lm_engine* env, int policy, const float*
   return 0;
 }
 
+int lm_rollout_set_deterministic(lm_rollout* r, int on) {
+  if (!r) return lm_internal_fail(-1, "lm_rollout_set_deterministic: null plan");
+  if (!lm_internal_on_device(r->env)) return lm_internal_fail(-1, "lm_rollout_set_deterministic: the calling thread's current device is not the engine's device");
+  r->det = on != 0;
+  return 0;
+}
+
+int lm_rollout_set_episode_record(lm_rollout* r, float* record, int episode_cap) {
+  if (!r) return lm_internal_fail(-1, "lm_rollout_set_episode_record: null plan");
+  if (!lm_internal_on_device(r->env)) return lm_internal_fail(-1, "lm_rollout_set_episode_record: the calling thread's current device is not the engine's device");
+  r->record = record; r->cap = episode_cap > 0 ? episode_cap : 0;
+  return 0;
+}
+
+int lm_episode_update(lm_engine* h, const float* rewards, const int64_t* dones, float* record, int episode_cap, void* stream) {
+  if (!h || !rewards || !dones || !record) return lm_internal_fail(-1, "lm_episode_update: null handle, rewards, dones or record");
+  if (!lm_internal_on_device(h)) return lm_internal_fail(-1, "lm_episode_update: the calling thread's current device is not the engine's device");
+  int split = 0, M[2] = {0, 0}; lm_internal_episode_info(h, &split, M);
+  const int N = lm_num_envs(h);
+  hipLaunchKernelGGL(k_episode_update, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, rewards, dones, (const int64_t*)lm_ptr(h, LM_PTR_CNT), N, split,
+                     M[0], M[1], record, episode_cap > 0 ? episode_cap : 0);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 int lm_rollout_run(lm_rollout* r, int use_graph, void* stream) {
   if (!r) return lm_internal_fail(-1, "lm_rollout_run: null plan");
   hipStream_t s = (hipStream_t)stream;
   if (use_graph == LM_ROLLOUT_AUTO)      // a persistent block holds a whole CU (512 registers per lane): one resident generation of blocks, or the graph
-    use_graph = (r->persistent_ok && lm_internal_rollout_supported(r->env, r->policy, r->nobs) && (r->N + 15) / 16 <= r->n_cu) ? LM_ROLLOUT_PERSISTENT : LM_ROLLOUT_GRAPH;      // asked again: contact-force reporting may have been switched on since
+    use_graph = (r->persistent_ok && lm_internal_rollout_supported(r->env, r->policy, r->nobs) && (!r->record || lm_internal_rollout_records(r->policy, r->nobs)) &&
+                 (r->N + 15) / 16 <= r->n_cu) ? LM_ROLLOUT_PERSISTENT : LM_ROLLOUT_GRAPH;      // asked again: contact-force reporting may have been switched on since
   if (!use_graph) return rollout_enqueue(r, s);
   if (use_graph == LM_ROLLOUT_PERSISTENT) {
     // the whole rollout in one kernel (un-randomised engines); same results as the other two modes
     LmRolloutArgs R; R.params = r->params; R.log_std = r->log_std; R.obs = r->obs; R.actions = r->actions; R.logp = r->logp; R.values = r->values;
     R.rewards = r->rewards; R.extras = r->extras; R.dones = r->dones; R.acc_steps = r->acc_steps; R.T = r->T; R.nobs = r->nobs; R.noise_seed = r->seed;
+    R.deterministic = r->det ? 1 : 0; R.record = r->record; R.episode_cap = r->cap;
     return lm_internal_rollout(r->env, r->policy, R, s);
   }
-  if (r->exec && r->exec_env_key != lm_internal_args_key(r->env)) {      // lm_set_seed / a first lm_ptr() for a view / lm_enable_contact_forces since the capture: the graph's kernel arguments are stale
+  if (r->exec && (r->exec_env_key != lm_internal_args_key(r->env) || r->exec_det != r->det || r->exec_record != r->record || r->exec_cap != r->cap)) {
+    // lm_set_seed / a first lm_ptr() for a view / lm_enable_contact_forces / a switch of the plan flipped since the capture: the graph's kernels or their arguments are stale
     (void)hipGraphExecDestroy(r->exec); r->exec = nullptr;
   }
   if (!r->exec) {
     // capture the 4T+1 launches once; every pointer in them is fixed for the lifetime of the plan
-    r->exec_env_key = lm_internal_args_key(r->env);
+    r->exec_env_key = lm_internal_args_key(r->env); r->exec_det = r->det; r->exec_record = r->record; r->exec_cap = r->cap;
     hipGraph_t g = nullptr;
     hipStream_t cs = s;
     bool own = false;

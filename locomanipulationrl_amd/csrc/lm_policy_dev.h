@@ -114,7 +114,28 @@ __device__ __forceinline__ uint32_t ro_key(const int64_t* __restrict__ cnt, int 
   return ((uint32_t)cnt[5 * (size_t)N + env] << 16) + (uint32_t)cnt[4 * (size_t)N + env];
 }
 struct SampleArgs { const float* log_std; const int64_t* cnt; uint32_t seed; float* actions; float* logp; };      // log_std == nullptr: no sampling
+// Deterministic plans (lm_rollout_set_deterministic) run instantiations of the tiles with DET = true: the action is the mean itself (never
+// fmaf(exp(ls), 0, mean): exp may overflow and inf * 0 is a NaN), its log-probability term is the stochastic expression at eps = 0, i.e.
+// -ls - ln sqrt(2 pi), summed in the same order; no normal is drawn, cnt and seed are not read.
+#define LM_LOGP_DET(ls) (-(ls) - 0.9189385332046727f)
 
+
+// ---- episode record (include/lm_policy.h, lm_rollout_set_episode_record): one env's update after a step.  rec[row * stride + i] is the env's
+// column of the float [LM_EPISODE_ROWS][.] record (the caller's buffer: stride N; the persistent kernels' LDS copy: stride 16).  r, d: the step's
+// reward and done flag; g: goal_reset_buf after the step; M: max_episode of the env's parameter block.  Plain fp32 adds in step order - no
+// products, so nothing contracts into an FMA - which is what makes every mode (and the host reference of the tests) agree bit for bit.
+__device__ __forceinline__ void episode_update(float* rec, size_t stride, size_t i, float r, bool d, bool g, int M, int cap) {
+  const float done = rec[2 * stride + i];
+  if (cap > 0 && done >= (float)cap) return;        // the first `cap` episodes of every env
+  float ret = rec[i] + r, len = rec[stride + i] + 1.0f;
+  if (d) {
+    rec[2 * stride + i] = done + 1.0f; rec[3 * stride + i] += ret; rec[4 * stride + i] += len;
+    const int how = g ? 5 : (len >= (float)(M - 1) ? 6 : 7);      // goal | timeout (also a failure on the very step the timeout fires) | failure
+    rec[how * stride + i] += 1.0f; rec[8 * stride + i] = ret;
+    ret = 0.0f; len = 0.0f;
+  }
+  rec[i] = ret; rec[stride + i] = len;
+}
 
 // ------------------------------------------------------------------------------------------------
 // MLP policy (scripts/skrl_ppo_locomotion.py:30-40): shared trunk 64 -> 256 -> 128 -> 64 (ELU) -> mean (12) + value (1),
@@ -266,7 +287,7 @@ struct MlpLayer {
 // LDS_OBS = false: `obs` is the global (B, NOBS) observation matrix.  LDS_OBS = true: `obs` is a [16][NOBS] tile in LDS holding the
 // UNCLIPPED observations of exactly these samples; they are clamped to +-obs_clip first, i.e. the values the step kernel returns.
 // mean may be null.  With SA.log_std set, wavefront 0 samples the actions and their log-probabilities in the epilogue.
-template <int NOBS, bool LDS_OBS>
+template <int NOBS, bool LDS_OBS, bool DET = false>
 __device__ __forceinline__ void mlp_block(const float* obs, float obs_clip, int B, int s0, const float* __restrict__ W, float* __restrict__ mean,
                                           float* __restrict__ value, const SampleArgs& SA, MlpSmem<NOBS>& M, int t) {
   const int wave = t >> 6, lane = t & 63, n = lane & 15, g = lane >> 4;
@@ -315,6 +336,9 @@ __device__ __forceinline__ void mlp_block(const float* obs, float obs_clip, int 
     const float v = sO[j * MLP_O_STRIDE + n];
     if (valid && j < 12 && mean) mean[(size_t)smp * 12 + j] = v;
     if (valid && j == 12) value[smp] = v;
+    if (DET) {
+      if (SA.log_std && j < 12 && valid) { SA.actions[(size_t)smp * 12 + j] = v; lp += LM_LOGP_DET(SA.log_std[j]); }
+    } else
     if (SA.log_std && j < 12 && valid) {
       const float ls = SA.log_std[j], eps = ro_normal(SA.seed, (uint32_t)smp, ro_key(SA.cnt, B, smp), (uint32_t)j);
       SA.actions[(size_t)smp * 12 + j] = fmaf(expf(ls), eps, v);
@@ -385,7 +409,7 @@ template <int NOBS, int P> struct MlpResRegs {
 };
 
 // one forward of samples s0 .. s0+15 by the policy wavefronts; tp = 0 .. 191 the thread index among them.  Same arithmetic, same order as mlp_block.
-template <int NOBS, int P, bool LDS_OBS>
+template <int NOBS, int P, bool LDS_OBS, bool DET = false>
 __device__ __forceinline__ void mlp_res_tile(const float* obs, float obs_clip, int B, int s0, const float* __restrict__ W, const MlpResRegs<NOBS, P>& R,
                                              float* __restrict__ value, const SampleArgs& SA, MlpSmem<NOBS>& M, int tp) {
   typedef MlpResRegs<NOBS, P> RG;
@@ -424,6 +448,9 @@ __device__ __forceinline__ void mlp_res_tile(const float* obs, float obs_clip, i
     const float m3 = __shfl(hv[3], n + 16 * P);
     const int j = (g < 3) ? 4 * g + P : 4 * P + 3;
     const float v = (g < 3) ? hv[P] : m3;
+    if (DET) {
+      if (SA.log_std && valid) { SA.actions[(size_t)smp * 12 + j] = v; M.sLp[j * 16 + n] = LM_LOGP_DET(SA.log_std[j]); }
+    } else
     if (SA.log_std && valid) {
       const float ls = SA.log_std[j], eps = ro_normal(SA.seed, (uint32_t)smp, ro_key(SA.cnt, B, smp), (uint32_t)j);
       SA.actions[(size_t)smp * 12 + j] = fmaf(expf(ls), eps, v);
@@ -505,7 +532,7 @@ __device__ __forceinline__ constexpr int gnn_ek(int w, int e) { int c = 0; for (
 
 // LDS_OBS = false: `obs` is the global (B, 64) observation matrix.  LDS_OBS = true: `obs` is a [16][64] tile in LDS with the UNCLIPPED
 // observations of samples s0 .. s0+15, clamped to +-obs_clip first (= the values the step kernel returns).  mean may be null.
-template <int WAVE, bool LDS_OBS>
+template <int WAVE, bool LDS_OBS, bool DET = false>
 __device__ __forceinline__ void gnn_body(const float* obs, float obs_clip, int B, int s0, const float* __restrict__ W, float* __restrict__ mean,
                                          float* __restrict__ value, const SampleArgs& SA, float* sPQ, float* sHm, float* sLp, const float* sOb, int lane) {
   constexpr int NC = gnn_count(WAVE);
@@ -697,6 +724,9 @@ __device__ __forceinline__ void gnn_body(const float* obs, float obs_clip, int B
     const float m = p + W[OFF_ACT_B];
     if (write) {
       if (mean) mean[(size_t)(s0 + n) * 12 + (nd - 1)] = m;
+      if (DET) {
+        if (SA.log_std) { const int a = nd - 1; SA.actions[(size_t)(s0 + n) * 12 + a] = m; sLp[a * GNN_SAMPLES + n] = LM_LOGP_DET(SA.log_std[a]); }
+      } else
       if (SA.log_std) {
         const int a = nd - 1, smp = s0 + n;
         const float ls = SA.log_std[a], eps = ro_normal(SA.seed, (uint32_t)smp, ro_key(SA.cnt, B, smp), (uint32_t)a);
@@ -746,7 +776,7 @@ struct GnnSmem {
   int rot;                                          // rotation of the wavefront -> node-set map of this block (gnn_block)
 };
 // forward of samples s0 .. s0+15 by the 256 threads of a block (contains block barriers)
-template <bool LDS_OBS>
+template <bool LDS_OBS, bool DET = false>
 __device__ __forceinline__ void gnn_block(const float* obs, float obs_clip, int B, int s0, const float* __restrict__ W, float* __restrict__ mean,
                                           float* __restrict__ value, const SampleArgs& SA, GnnSmem& G, int t) {
   const int lane = t & 63;
@@ -774,9 +804,9 @@ __device__ __forceinline__ void gnn_block(const float* obs, float obs_clip, int 
   }
   lds_barrier();
   const int wave = ((t >> 6) + G.rot) & 3;
-  if (wave == 0) gnn_body<0, LDS_OBS>(obs, obs_clip, B, s0, W, mean, value, SA, G.sPQ, G.sHm, G.sLp, G.sOb, lane);
-  else if (wave == 1) gnn_body<1, LDS_OBS>(obs, obs_clip, B, s0, W, mean, value, SA, G.sPQ, G.sHm, G.sLp, G.sOb, lane);
-  else if (wave == 2) gnn_body<2, LDS_OBS>(obs, obs_clip, B, s0, W, mean, value, SA, G.sPQ, G.sHm, G.sLp, G.sOb, lane);
-  else gnn_body<3, LDS_OBS>(obs, obs_clip, B, s0, W, mean, value, SA, G.sPQ, G.sHm, G.sLp, G.sOb, lane);
+  if (wave == 0) gnn_body<0, LDS_OBS, DET>(obs, obs_clip, B, s0, W, mean, value, SA, G.sPQ, G.sHm, G.sLp, G.sOb, lane);
+  else if (wave == 1) gnn_body<1, LDS_OBS, DET>(obs, obs_clip, B, s0, W, mean, value, SA, G.sPQ, G.sHm, G.sLp, G.sOb, lane);
+  else if (wave == 2) gnn_body<2, LDS_OBS, DET>(obs, obs_clip, B, s0, W, mean, value, SA, G.sPQ, G.sHm, G.sLp, G.sOb, lane);
+  else gnn_body<3, LDS_OBS, DET>(obs, obs_clip, B, s0, W, mean, value, SA, G.sPQ, G.sHm, G.sLp, G.sOb, lane);
 }
 

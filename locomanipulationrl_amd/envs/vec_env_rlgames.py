@@ -22,6 +22,11 @@ class VecEnvRLGames(VecEnvBase):
         self.num_states = self._task.num_states
         self.state_space = self._task.state_space
 
+    @property
+    def unwrapped(self):
+        """The base environment (gym.Env.unwrapped): the reference's scripts reach the task as env._env.unwrapped._task."""
+        return self
+
     def step(self, actions):
         if self._task.randomize_actions:
             actions = self._task._dr_randomizer.apply_actions_randomization(actions=actions, reset_buf=self._task.reset_buf)

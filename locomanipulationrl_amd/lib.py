@@ -22,13 +22,17 @@ DR_RESET_CHANNELS, DR_RESET_ROWS = 4, 31      # LM_DR_RESET_CHANNELS, LM_DR_RESE
 DR_MASS_CHANNELS, DR_MASS_ROWS, NUM_BODIES = 3, 23, 21      # LM_DR_MASS_CHANNELS, LM_DR_MASS_ROWS, LM_NUM_BODIES
 DR_ACTUATOR_CHANNELS, DR_ACTUATOR_ROWS = 3, 3      # LM_DR_ACTUATOR_CHANNELS, LM_DR_ACTUATOR_ROWS
 CONTACT_ROWS = 16        # LM_CONTACT_ROWS
+EPISODE_ROWS = 9         # LM_EPISODE_ROWS (include/lm_policy.h)
+# rows of the episode record
+EPISODE = dict(running_return=0, running_length=1, episodes=2, sum_return=3, sum_length=4, goal=5, timeout=6, failure=7, last_return=8)
 PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS, PTR_CONTACT, PTR_DR_ACTUATOR = range(14)
 
 # names of the exported C symbols (checked by tests/test_abi.py against include/lm_engine.h)
 EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass_randomization", "lm_set_actuator_randomization", "lm_enable_contact_forces", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
            "lm_forward_kinematics", "lm_debug_dynamics", "lm_ptr", "lm_num_envs", "lm_num_obs", "lm_set_seed", "lm_last_error", "lm_version", "lm_abi_version",
            "lm_gnn_param_count", "lm_gnn_forward", "lm_mlp_param_count", "lm_mlp_forward", "lm_mlp_param_count_obs", "lm_mlp_forward_obs",
-           "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy"]
+           "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy",
+           "lm_rollout_set_deterministic", "lm_rollout_set_episode_record", "lm_episode_update"]
 
 # rows of the SoA float state
 ROW = dict(base_pos=0, base_quat=3, base_lin=7, base_ang=10, q=13, qd=25, plate_pos=37, plate_quat=40, plate_lin=44,
@@ -189,7 +193,8 @@ def hipcc_command(extra, out):
     # -amdgpu-mfma-vgpr-form: the MFMA accumulators of the policy tiles live in ordinary VGPRs, so the VALU work on them (ELU, max aggregation,
     # LDS stores) needs no v_accvgpr_read per element (504 of them in k_gnn_forward)
     return [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
-            "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_policy.hip"), "-o", out]
+            "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"),
+            os.path.join(_CSRC, "lm_policy.hip"), "-o", out]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -245,6 +250,9 @@ def load_library() -> C.CDLL:
     lib.lm_rollout_create.argtypes = [C.POINTER(vp), vp, ip, fp, fp, ip, C.c_uint32, fp, fp, fp, fp, fp, vp, fp]
     lib.lm_rollout_run.argtypes = [vp, ip, vp]
     lib.lm_rollout_destroy.argtypes = [vp]
+    lib.lm_rollout_set_deterministic.argtypes = [vp, ip]
+    lib.lm_rollout_set_episode_record.argtypes = [vp, fp, ip]
+    lib.lm_episode_update.argtypes = [vp, fp, vp, fp, ip, vp]
     lib.lm_last_error.restype = C.c_char_p
     lib.lm_version.restype = C.c_char_p
     _lib = lib
@@ -295,6 +303,7 @@ class Engine:
                     with torch.cuda.device(self.device):
                         self._check(getattr(self.lib, setter)(self._h, b, C.byref(dr)))
         self.seed = int(seed) & 0xFFFFFFFF
+        self.split_env = int(split_env) if (split_env and len(params) == 2) else None      # first env of the second parameter block (co-training)
         N = self.num_envs
         self.state = self._wrap(PTR_STATE, (STATE_ROWS, N), "<f4")
         self.cnt = self._wrap(PTR_CNT, (CNT_ROWS, N), "<i8")
@@ -552,9 +561,14 @@ class Rollout:
     """T steps of  policy forward (MFMA) -> gaussian sampling -> lm_step  recorded into rollout buffers and replayed as one hipGraph
     (include/lm_policy.h).  `packed_params` / `log_std` are device tensors read at run time: refresh them in place
     between runs.  Buffers: obs (T+1,N,64) with obs[0] = current observations, actions (T,N,12), logp (T,N), values (T+1,N),
-    rewards (T,N), dones int64 (T,N), extras (T,13)."""
+    rewards (T,N), dones int64 (T,N), extras (T,13).
 
-    def __init__(self, engine: Engine, policy: int, packed_params, log_std, T: int, noise_seed: int = 0):
+    Evaluation switches (both off by default; a plan that uses neither runs the kernels it always ran): `deterministic` makes actions[t] the
+    forward's mean and logp[t] the density at the mean; `episode_record` (an EpisodeRecord or a float (9, N) device tensor) is updated after
+    every step, for the first `episode_cap` episodes of each env when the cap is positive."""
+
+    def __init__(self, engine: Engine, policy: int, packed_params, log_std, T: int, noise_seed: int = 0, deterministic: bool = False,
+                 episode_record=None, episode_cap: int = 0):
         torch = engine.torch
         self.engine, self.T, self.N = engine, int(T), engine.num_envs
         assert engine.num_obs == 64 or (engine.num_obs == 88 and policy == POLICY_MLP), "the GNN reads the 64-wide layout; the MLP 64 or 88"
@@ -574,6 +588,30 @@ class Rollout:
                                           p(self.obs), p(self.actions), p(self.logp), p(self.values), p(self.rewards), p(self.dones), p(self.extras))
         if rc != 0:
             raise EngineError(f"lm_rollout_create failed ({rc})")
+        self.deterministic, self.episode_record, self.episode_cap = False, None, 0
+        if deterministic:
+            self.set_deterministic(True)
+        if episode_record is not None:
+            self.set_episode_record(episode_record, episode_cap)
+
+    def _set(self, rc):
+        if rc != 0:
+            raise EngineError(f"lm_engine error {rc}: {self.engine.lib.lm_last_error().decode()}")
+
+    def set_deterministic(self, on: bool = True):
+        """Mean actions from the next run on (a captured graph is re-captured)."""
+        with self.engine.torch.cuda.device(self.engine.device):
+            self._set(self.engine.lib.lm_rollout_set_deterministic(self._h, 1 if on else 0))
+        self.deterministic = bool(on)
+
+    def set_episode_record(self, record=None, episode_cap: int = 0):
+        """Attach an EpisodeRecord / a float (9, N) device tensor (None: recording off) from the next run on; the plan keeps it alive."""
+        t = getattr(record, "record", record)
+        if t is not None:
+            self.engine._f32(t, (EPISODE_ROWS, self.N))
+        with self.engine.torch.cuda.device(self.engine.device):
+            self._set(self.engine.lib.lm_rollout_set_episode_record(self._h, Engine._p(t), int(episode_cap)))
+        self.episode_record, self.episode_cap = record, int(episode_cap)
 
     MODES = {"enqueue": 0, "graph": 1, "persistent": 2, "auto": 3}
 
@@ -607,3 +645,68 @@ def sample_actions(engine: Engine, mean, log_std, seed: int):
     if rc != 0:
         raise EngineError(f"lm_sample_actions failed ({rc})")
     return act, logp
+
+
+class EpisodeRecord:
+    """The episode record of include/lm_policy.h: a float (9, N) tensor on the engine's device - per env the running return and length, the
+    episodes completed, the sums of their returns and lengths, how they ended (goal / timeout / failure) and the last return (rows: EPISODE).
+    Hand it to a Rollout (episode_record=) or call update() after every engine step; zero() starts a measurement.  On an engine without
+    the C library (CPU tensors: the oracle backend of the tests) update() applies the same rule in torch."""
+
+    def __init__(self, engine):
+        import torch
+        self.torch, self.engine, self.N = torch, engine, int(engine.num_envs)
+        self.record = torch.zeros((EPISODE_ROWS, self.N), dtype=torch.float32, device=engine.cnt.device)
+        self._native = hasattr(engine, "lib") and hasattr(engine, "_h")
+        if self._native:
+            self.split = engine.split_env
+        else:                     # a backend with the engine's interface and its parameter blocks on the host
+            params = list(engine.params)
+            self.split = int(engine.split) if len(params) == 2 else None
+            m = torch.full((self.N,), float(params[0].max_episode))
+            if self.split:
+                m[self.split:] = float(params[1].max_episode)
+            self._max_episode = m.to(self.record.device)
+
+    def zero(self):
+        self.record.zero_()
+
+    def update(self, rew, resets, episode_cap: int = 0):
+        """One step: rew (N,) float32 and resets (N,) int64 as step() returned them; the goal flag is the engine's goal_reset_buf."""
+        e, torch = self.engine, self.torch
+        if self._native:
+            rew = e._f32(rew, (self.N,))
+            assert resets.dtype == torch.int64 and resets.is_contiguous() and resets.device == e.device and tuple(resets.shape) == (self.N,)
+            with torch.cuda.device(e.device):
+                e._check(e.lib.lm_episode_update(e._h, Engine._p(rew), Engine._p(resets), Engine._p(self.record), int(episode_cap), e._stream()))
+            return
+        R = self.record
+        live = torch.ones(self.N, dtype=torch.bool, device=R.device) if episode_cap <= 0 else R[2] < float(episode_cap)
+        d = (resets != 0) & live
+        g = e.cnt[2].to(R.device) != 0
+        ret = torch.where(live, R[0] + rew.to(R.device, torch.float32), R[0]); length = torch.where(live, R[1] + 1.0, R[1])
+        one = d.to(torch.float32)
+        R[2] += one; R[3] = torch.where(d, R[3] + ret, R[3]); R[4] = torch.where(d, R[4] + length, R[4])
+        timeout = length >= (self._max_episode - 1.0)
+        R[5] += (d & g).to(torch.float32); R[6] += (d & ~g & timeout).to(torch.float32); R[7] += (d & ~g & ~timeout).to(torch.float32)
+        R[8] = torch.where(d, ret, R[8])
+        R[0] = torch.where(d, torch.zeros_like(ret), ret); R[1] = torch.where(d, torch.zeros_like(length), length)
+
+    @staticmethod
+    def _reduce(rec):
+        n = float(rec[2].sum())
+        div = lambda x: float(x) / n if n > 0 else float("nan")
+        return {"episodes": int(n), "mean_return": div(rec[3].sum()), "mean_length": div(rec[4].sum()), "success_rate": div(rec[5].sum()),
+                "timeout_rate": div(rec[6].sum()), "failure_rate": div(rec[7].sum()), "goals": int(rec[5].sum()), "timeouts": int(rec[6].sum()),
+                "failures": int(rec[7].sum())}
+
+    def summary(self, split=None):
+        """Host reduction in float64 over the envs: episodes, mean_return, mean_length, success_rate (goal / episodes), timeout_rate,
+        failure_rate (and the three counts).  With `split` (the first env of a co-training engine's second block) the same per half under
+        "loco" and "mani"."""
+        rec = self.record.detach().cpu().double().numpy()
+        out = self._reduce(rec)
+        split = self.split if split is None else split
+        if split:
+            out["loco"] = self._reduce(rec[:, :split]); out["mani"] = self._reduce(rec[:, split:])
+        return out

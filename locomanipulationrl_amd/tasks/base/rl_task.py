@@ -170,12 +170,12 @@ class RLTask:
     def load_state_dict(self, sd) -> None:
         self.engine.load_state_dict(sd)
 
-    def make_rollout(self, policy: str, packed_params: torch.Tensor, log_std: torch.Tensor, T: int, noise_seed: int = 0):
+    def make_rollout(self, policy: str, packed_params: torch.Tensor, log_std: torch.Tensor, T: int, noise_seed: int = 0, **switches):
         """A fused T-step rollout (policy forward -> sampling -> step, one hipGraph launch; include/lm_policy.h)."""
         from ...lib import POLICY_GNN, POLICY_MLP, Rollout
         if self._goal_rng != "engine":
             raise NotImplementedError("the fused rollout samples goals with the in-kernel generator (env.goalSampler: engine)")
-        return Rollout(self.engine, {"mlp": POLICY_MLP, "gnn": POLICY_GNN}[policy], packed_params, log_std, T, noise_seed)
+        return Rollout(self.engine, {"mlp": POLICY_MLP, "gnn": POLICY_GNN}[policy], packed_params, log_std, T, noise_seed, **switches)
 
     def _publish(self, out):
         obs, states, rew, resets, extras = out
@@ -219,6 +219,10 @@ class RLTask:
 
     def get_states(self):
         return self._last_states
+
+    def get_extras(self):
+        """The extras dict of the last step (rl_task.py:219-226)."""
+        return self.extras
 
     def reset(self):
         """Flags all envs for reset (rl_task.py:227-230)."""

@@ -40,6 +40,14 @@ class RunningStandardScaler:
         m2 = self.var * self.count + bvar * n + delta * delta * self.count * n / tot
         self.mean = self.mean + delta * n / tot; self.var = m2 / tot; self.count = tot
 
+    def state_dict(self):
+        return {"mean": self.mean.detach().cpu().clone(), "var": self.var.detach().cpu().clone(), "count": self.count.detach().cpu().clone()}
+
+    def load_state_dict(self, sd):
+        dev = self.mean.device
+        assert tuple(sd["mean"].shape) == tuple(self.mean.shape), (tuple(sd["mean"].shape), tuple(self.mean.shape))
+        self.mean, self.var, self.count = (sd[k].to(dev, torch.float64).clone() for k in ("mean", "var", "count"))
+
     def __call__(self, x: torch.Tensor, inverse: bool = False):
         mean, std = self.mean.float(), self.var.float().sqrt()
         if inverse:
@@ -165,6 +173,27 @@ class PPO:
             for gp in self.opt.param_groups: gp["lr"] = self.lr
             stats = {"kl": kl, "loss_pi": float(loss_pi), "loss_v": float(loss_v), "lr": self.lr}
         return stats
+
+    # ------------------------------------------------------------------ checkpoints (what the reference's agents write as best_agent.pt: policy,
+    # value head, optimiser and both preprocessors; tools/eval_policy.py and train/evaluate.py read them back)
+    def state_dict(self):
+        return {"model": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}, "model_class": type(self.model).__name__,
+                "num_observations": self.n_obs, "obs_scaler": self.obs_scaler.state_dict(), "val_scaler": self.val_scaler.state_dict(),
+                "lr": float(self.lr), "optimizer": self.opt.state_dict()}
+
+    def load_state_dict(self, sd):
+        assert int(sd["num_observations"]) == self.n_obs, (sd["num_observations"], self.n_obs)
+        self.model.load_state_dict(sd["model"])
+        self.obs_scaler.load_state_dict(sd["obs_scaler"]); self.val_scaler.load_state_dict(sd["val_scaler"])
+        self.opt.load_state_dict(sd["optimizer"])
+        self.lr = float(sd["lr"])
+        for gp in self.opt.param_groups: gp["lr"] = self.lr
+
+    def save(self, path):
+        torch.save(self.state_dict(), path)
+
+    def load(self, path):
+        self.load_state_dict(torch.load(path, map_location="cpu", weights_only=False))
 
     def train(self, timesteps: int, log_every: int = 10, log=print):
         obs = self.env.reset()["obs"]; history = []; t0 = time.perf_counter()

@@ -1,0 +1,44 @@
+#!/usr/bin/env python3
+"""Evaluate a checkpoint written by tools/train_ppo.py --save: mean actions (the reference's eval = True / agent.set_mode('eval')),
+the first --episodes-per-env episodes of every env, one JSON line with the summary (episodes, mean_return, mean_length, success_rate,
+timeout_rate, failure_rate, ...; co-training tasks also per half).
+    python tools/eval_policy.py --checkpoint agent.pt --task QuadrupedPoseControl [--num-envs 4096 --episodes-per-env 1 --stochastic --randomize]"""
+import argparse, json, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import locomanipulationrl_amd as lm
+from locomanipulationrl_amd.train.evaluate import evaluate
+from locomanipulationrl_amd.train.ppo import RunningStandardScaler
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--checkpoint", required=True); ap.add_argument("--task", default="QuadrupedPoseControl")
+    ap.add_argument("--num-envs", type=int, default=4096); ap.add_argument("--episodes-per-env", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=42); ap.add_argument("--max-steps", type=int, default=None)
+    ap.add_argument("--stochastic", action="store_true", help="sample actions as in training instead of taking the mean")
+    ap.add_argument("--randomize", action="store_true", help="switch the task YAML's domain_randomization block on")
+    ap.add_argument("--no-fused", action="store_true", help="step from Python instead of the fused rollout")
+    a = ap.parse_args()
+    sd = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
+    torch.manual_seed(a.seed)
+    env = lm.make_env(a.task, num_envs=a.num_envs, seed=a.seed,
+                      overrides={"task": {"domain_randomization": {"randomize": True}} if a.randomize else {}})
+    n_obs = int(env.observation_space.shape[0])
+    if int(sd["num_observations"]) != n_obs:
+        raise SystemExit(f"the checkpoint was trained on {sd['num_observations']}-wide observations, {a.task} has {n_obs}")
+    if sd["model_class"] == "GraphPolicy":
+        from locomanipulationrl_amd.policies.graph_model import GraphPolicy
+        model = GraphPolicy()
+    else:
+        from locomanipulationrl_amd.policies.mlp_model import SharedMLP
+        model = SharedMLP(num_observations=n_obs)
+    model.load_state_dict(sd["model"]); model = model.to("cuda:0")
+    scaler = RunningStandardScaler(n_obs, "cuda:0"); scaler.load_state_dict(sd["obs_scaler"])
+    out = evaluate(env, model, scaler, episodes_per_env=a.episodes_per_env, max_steps=a.max_steps, deterministic=not a.stochastic, fused=not a.no_fused)
+    print(json.dumps({"task": a.task, "num_envs": a.num_envs, "checkpoint": a.checkpoint, **out}), flush=True)
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -5,7 +5,8 @@
 
 Exports REV with `git archive`, builds that tree and the working tree with their own lib.hipcc_command(...) plus --save-temps, each in a temporary
 directory, and compares per kernel of every translation unit the text between the kernel's label and its .Lfunc_end and its .amdhsa_kernel block
-(lines naming __hip_cuid_, a per-unit symbol hashed from the source path, are ignored).  Prints each kernel's resources; exits 1 on any difference.
+(lines naming __hip_cuid_, a per-unit symbol hashed from the source path, are ignored; so are comments, and local labels are compared without
+the index of their function in the unit, which moves when a kernel is added in front of it).  Prints each kernel's resources; exits 1 on any difference.
 A refactor of the engine source is done when this prints no DIFFERS for the product build and for every diagnostic switch the tools build with
 (-DLM_STAMPS=1, -DLM_STAMPS=2, -DLM_COUNT_PASS2, -DLM_WAVES2)."""
 import concurrent.futures
@@ -34,7 +35,11 @@ def device_asm(tree, extra, work):
 
 def kernels(asm):
     """{kernel: (body lines, .amdhsa_kernel block lines)} of one unit's assembly."""
-    keep = lambda text: [ln for ln in text.split("\n") if "__hip_cuid_" not in ln]
+    def keep(text):
+        # instructions only: comments carry the names of inlined device functions, and a local label carries the index of its function in the
+        # unit (.LBB<function>_<block>, .Lpost_getpc<n>), which moves when a kernel is added in front of it; neither changes an instruction
+        lines = (re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", re.sub(r"\.LBB\d+_", ".LBB_", ln.split(";")[0].rstrip())) for ln in text.split("\n") if "__hip_cuid_" not in ln)
+        return [ln for ln in lines if ln]
     out = {}
     for m in re.finditer(r"^(\w+):[^\n]*\n(.*?)^\s*\.amdhsa_kernel \1\n(.*?)^\s*\.end_amdhsa_kernel\n(.*?)^\.Lfunc_end\d+:", asm, re.M | re.S):
         out[m.group(1)] = (keep(m.group(2) + m.group(4)), keep(m.group(3)))

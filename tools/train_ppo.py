@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Behavioural acceptance run: train the reference's PPO recipe on the engine and log the success-rate curve.
-    python tools/train_ppo.py --task QuadrupedPoseControl --num-envs 4096 --timesteps 4800 [--policy mlp|gnn] [--out profiles/x.json]
+    python tools/train_ppo.py --task QuadrupedPoseControl --num-envs 4096 --timesteps 4800 [--policy mlp|gnn] [--out profiles/x.json] [--save agent.pt]
 (multi-GPU: python -m torch.distributed.run --nproc-per-node N tools/train_ppo.py ...)"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,6 +15,7 @@ def main():
     ap.add_argument("--task", default="QuadrupedPoseControl"); ap.add_argument("--num-envs", type=int, default=4096)
     ap.add_argument("--timesteps", type=int, default=4800); ap.add_argument("--policy", default="mlp"); ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--out", default=""); ap.add_argument("--log-every", type=int, default=5)
+    ap.add_argument("--save", default="", metavar="PATH", help="write the trained agent (policy, both scalers, optimiser) here: tools/eval_policy.py --checkpoint PATH evaluates it")
     ap.add_argument("--randomize", action="store_true", help="switch the task YAML's domain_randomization block on (the reference's YAMLs ship it with randomize: False)")
     ap.add_argument("--fixed-lr", action="store_true", help="no KL-adaptive learning rate (diagnostics; not the reference recipe)")
     ap.add_argument("--gnn-env-order", action="store_true", help="diagnostic: route GNN node k's output to the joint whose state node k reads (the reference feeds node order straight to the env)")
@@ -53,6 +54,8 @@ def main():
     hist = ppo.train(a.timesteps, log_every=a.log_every, log=(lambda r: print(json.dumps(r), flush=True)) if rank == 0 else (lambda r: None))
     if rank == 0 and a.out:
         json.dump({"task": a.task, "num_envs": a.num_envs, "world": world, "policy": a.policy, "history": hist}, open(a.out, "w"), indent=1)
+    if rank == 0 and a.save:
+        ppo.save(a.save)
     env.close()
 
 
