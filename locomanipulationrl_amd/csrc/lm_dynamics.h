@@ -370,8 +370,9 @@ LM_DEV void integrate_free(FreeBody& F, const M3& R, float dt) {
   F.p = fma3(dt, mul(Rn, F.u.v), F.p);
 }
 
-// Per-lane stash in LDS for the pass-invariant terms of a sub-step (they are needed at the top of each of the two
-// drive passes but not during the contact iterations; keeping them in registers across the PGS loop spills).
+// Per-lane stash in LDS for the pass-invariant terms of a sub-step (the SECOND drive pass needs them again after the contact
+// iterations of the first; keeping them in registers across the PGS loop spills.  The first pass runs on the registers
+// they were computed in, see PassTerms; k_step_w2 and the persistent rollouts read them back in both passes).
 // Layout [slot][lane] as float4 -> conflict-free 16-byte accesses.
 #ifdef LM_WAVES2
 // k_step compiled for TWO wavefronts per SIMD.  That needs <= 256 registers per lane (amdgpu_waves_per_eu(2, 2): the
@@ -402,6 +403,97 @@ LM_DEV void unstash_sv3(const Stash& S, int slot, SV& a, SV& b, SV& c) {
   a = sv(v3(t0.x, t0.y, t0.z), v3(t0.w, t1.x, t1.y)); b = sv(v3(t1.z, t1.w, t2.x), v3(t2.y, t2.z, t2.w)); c = sv(v3(t3.x, t3.y, t3.z), v3(t3.w, t4.x, t4.y));
 }
 
+// The pass-invariant terms of a sub-step, in the register layout the pass reads them in.  substep() computes them, writes them to the stash and
+// runs the FIRST pass on the registers it has just computed; only a second pass (the active-set re-solve) reloads them from the stash, after the
+// contact iterations - keeping them in registers across those would spill.  Until round 5 the first pass reloaded them too: 19 ds_read_b128
+// behind 19 ds_write_b128 per sub-step, for values that were in registers (-DLM_PASS0_STASH: that form, tools/ab_build.py; substep<..., REG0 = 0>:
+// that form for one kernel - k_step_w2 and the persistent rollouts, whose scratch grows with the register form: DESIGN.md 5.1).
+#if defined(LM_PASS0_STASH) || defined(LM_WAVES2)      // (two wavefronts per SIMD: 256 registers have no room for the register form, see REG0)
+#define LM_PASS0_REG 0
+#else
+#define LM_PASS0_REG 1
+#endif
+struct PassTerms {
+  S6 Fq0, Fq1, Fq2;        // coupling columns
+  float Ha[6], hq[3];      // limb joint-space inertia [00,01,02,11,12,22] and bias
+  float Jq0[3]; f2 j12[3]; // tip velocity per unit joint rate, contact coordinates: row 0, rows (1 | 2)
+  R4 PB[6];                // p = (fcs[i] | Jb0[i]) or (up_free[i] | Tp0[i]),  q = (row 1 | row 2)
+  SI Isc;                  // limb composite inertia (MODE 0 only)
+};
+LM_DEV S6 s6(SV a) { S6 r; r.a = mk2(a.w.x, a.w.y); r.b = mk2(a.w.z, a.v.x); r.c = mk2(a.v.y, a.v.z); return r; }
+// (a macro on substep()'s own locals: as a function taking the SVs by reference, the pair (b.w.x | r0.w.x) is formed by a two-float load from b
+// before b is inlined, and b then stays in memory)
+#define LM_PASS_ROWS(I, b, r0, r1, r2) { \
+  I.PB[0].p = mk2(b.w.x, r0.w.x); I.PB[1].p = mk2(b.w.y, r0.w.y); I.PB[2].p = mk2(b.w.z, r0.w.z); \
+  I.PB[3].p = mk2(b.v.x, r0.v.x); I.PB[4].p = mk2(b.v.y, r0.v.y); I.PB[5].p = mk2(b.v.z, r0.v.z); \
+  I.PB[0].q = mk2(r1.w.x, r2.w.x); I.PB[1].q = mk2(r1.w.y, r2.w.y); I.PB[2].q = mk2(r1.w.z, r2.w.z); \
+  I.PB[3].q = mk2(r1.v.x, r2.v.x); I.PB[4].q = mk2(r1.v.y, r2.v.y); I.PB[5].q = mk2(r1.v.z, r2.v.z); }
+// The terms as the stash would hand them back: values in registers that the optimiser cannot see through, so that no expression of the pass is
+// contracted with the expression that produced one of its inputs.  The first pass then rounds exactly as a pass fed from the stash (costs no instruction)
+LM_DEV void pin(float& x) { asm("" : "+v"(x)); }
+LM_DEV void pin(f2& x) { asm("" : "+v"(x)); }
+LM_DEV void pin(S6& x) { pin(x.a); pin(x.b); pin(x.c); }
+template <int MODE> LM_DEV void pin_terms(PassTerms& I) {
+  // (no loops over the members: an index that is a variable until the loop is unrolled keeps the whole struct in memory too long)
+  pin(I.Fq0); pin(I.Fq1); pin(I.Fq2);
+  pin(I.Ha[0]); pin(I.Ha[1]); pin(I.Ha[2]); pin(I.Ha[3]); pin(I.Ha[4]); pin(I.Ha[5]);
+  pin(I.hq[0]); pin(I.hq[1]); pin(I.hq[2]); pin(I.Jq0[0]); pin(I.Jq0[1]); pin(I.Jq0[2]); pin(I.j12[0]); pin(I.j12[1]); pin(I.j12[2]);
+  pin(I.PB[0].p); pin(I.PB[1].p); pin(I.PB[2].p); pin(I.PB[3].p); pin(I.PB[4].p); pin(I.PB[5].p);
+  pin(I.PB[0].q); pin(I.PB[1].q); pin(I.PB[2].q); pin(I.PB[3].q); pin(I.PB[4].q); pin(I.PB[5].q);
+  if (MODE == 0) { pin(I.Isc.m); pin(I.Isc.h.x); pin(I.Isc.h.y); pin(I.Isc.h.z); pin(I.Isc.xx); pin(I.Isc.yy); pin(I.Isc.zz); pin(I.Isc.xy); pin(I.Isc.xz); pin(I.Isc.yz); }
+}
+// Stash layout: slots 0-4 Fq0..2 (LM_WAVES2: Isc.xz, Isc.yz ride in the free half of slot 4), 5-6 H and hq[0..1], 7 (hq[2] | Jq row 0), 8-9 Jq rows
+// (1 | 2), 10-12 PB[i].p, 13-15 PB[i].q, MODE 0: 16-18 Isc
+LM_DEV void put2(const Stash& St, int slot, f2 a, f2 b) { St.put(slot, a.x, a.y, b.x, b.y); }
+template <int MODE> LM_DEV void stash_terms(const Stash& St, const PassTerms& I) {
+  put2(St, 0, I.Fq0.a, I.Fq0.b); put2(St, 1, I.Fq0.c, I.Fq1.a); put2(St, 2, I.Fq1.b, I.Fq1.c); put2(St, 3, I.Fq2.a, I.Fq2.b);
+#ifdef LM_WAVES2
+  St.put(4, I.Fq2.c.x, I.Fq2.c.y, I.Isc.xz, I.Isc.yz);
+#else
+  St.put(4, I.Fq2.c.x, I.Fq2.c.y, 0.f, 0.f);
+#endif
+  St.put(5, I.Ha[0], I.Ha[1], I.Ha[2], I.Ha[3]); St.put(6, I.Ha[4], I.Ha[5], I.hq[0], I.hq[1]);
+  St.put(7, I.hq[2], I.Jq0[0], I.Jq0[1], I.Jq0[2]);
+  put2(St, 8, I.j12[0], I.j12[1]); put2(St, 9, I.j12[2], sp2(0.f));
+  put2(St, 10, I.PB[0].p, I.PB[1].p); put2(St, 11, I.PB[2].p, I.PB[3].p); put2(St, 12, I.PB[4].p, I.PB[5].p);
+  put2(St, 13, I.PB[0].q, I.PB[1].q); put2(St, 14, I.PB[2].q, I.PB[3].q); put2(St, 15, I.PB[4].q, I.PB[5].q);
+  if (MODE == 0) {
+    St.put(16, I.Isc.m, I.Isc.h.x, I.Isc.h.y, I.Isc.h.z); St.put(17, I.Isc.xx, I.Isc.yy, I.Isc.zz, I.Isc.xy);
+#ifndef LM_WAVES2
+    St.put(18, I.Isc.xz, I.Isc.yz, 0.f, 0.f);
+#endif
+  }
+}
+template <int MODE> LM_DEV void unstash_terms(const Stash& St, PassTerms& I) {
+  asm volatile("" ::: "memory");          // keep the stash reloads where the pass that needs them starts (no hoisting across the PGS loop)
+  float isc_xz = 0.f, isc_yz = 0.f;
+  {
+    const float4 t0 = St.get(0), t1 = St.get(1), t2 = St.get(2), t3 = St.get(3), t4 = St.get(4);
+    isc_xz = t4.z; isc_yz = t4.w;
+    I.Fq0.a = mk2(t0.x, t0.y); I.Fq0.b = mk2(t0.z, t0.w); I.Fq0.c = mk2(t1.x, t1.y);
+    I.Fq1.a = mk2(t1.z, t1.w); I.Fq1.b = mk2(t2.x, t2.y); I.Fq1.c = mk2(t2.z, t2.w);
+    I.Fq2.a = mk2(t3.x, t3.y); I.Fq2.b = mk2(t3.z, t3.w); I.Fq2.c = mk2(t4.x, t4.y);
+  }
+  const float4 h5 = St.get(5), h6 = St.get(6), h7 = St.get(7), h8 = St.get(8), h9 = St.get(9);
+  I.Ha[0] = h5.x; I.Ha[1] = h5.y; I.Ha[2] = h5.z; I.Ha[3] = h5.w; I.Ha[4] = h6.x; I.Ha[5] = h6.y;
+  I.hq[0] = h6.z; I.hq[1] = h6.w; I.hq[2] = h7.x;
+  I.Jq0[0] = h7.y; I.Jq0[1] = h7.z; I.Jq0[2] = h7.w;
+  I.j12[0] = mk2(h8.x, h8.y); I.j12[1] = mk2(h8.z, h8.w); I.j12[2] = mk2(h9.x, h9.y);
+  {
+    const float4 g0 = St.get(10), g1 = St.get(11), g2 = St.get(12), g3 = St.get(13), g4 = St.get(14), g5 = St.get(15);
+    I.PB[0].p = mk2(g0.x, g0.y); I.PB[1].p = mk2(g0.z, g0.w); I.PB[2].p = mk2(g1.x, g1.y); I.PB[3].p = mk2(g1.z, g1.w); I.PB[4].p = mk2(g2.x, g2.y); I.PB[5].p = mk2(g2.z, g2.w);
+    I.PB[0].q = mk2(g3.x, g3.y); I.PB[1].q = mk2(g3.z, g3.w); I.PB[2].q = mk2(g4.x, g4.y); I.PB[3].q = mk2(g4.z, g4.w); I.PB[4].q = mk2(g5.x, g5.y); I.PB[5].q = mk2(g5.z, g5.w);
+  }
+  if (MODE == 0) {
+#ifdef LM_WAVES2
+    const float4 g16 = St.get(16), g17 = St.get(17), g18 = make_float4(isc_xz, isc_yz, 0.f, 0.f);
+#else
+    const float4 g16 = St.get(16), g17 = St.get(17), g18 = St.get(18); (void)isc_xz; (void)isc_yz;
+#endif
+    I.Isc.m = g16.x; I.Isc.h = v3(g16.y, g16.z, g16.w); I.Isc.xx = g17.x; I.Isc.yy = g17.y; I.Isc.zz = g17.z; I.Isc.xy = g17.w; I.Isc.xz = g18.x; I.Isc.yz = g18.y;
+  }
+}
+
 // Per-env plate inertia of the randomised kernels (mass channels): the plate's inertia about its COM is diagonal, so the inverse of its spatial
 // inertia about the plate origin is  X^-1 diag(1 / I_com, 1 / m) X^-T  with X the shift by the COM: seven numbers instead of a 6 x 6 matrix.
 // For a wrench (n about the origin, f):  alpha = (n - c x f) / I_com,  a_origin = f / m + c x alpha
@@ -423,11 +515,147 @@ LM_DEV SI plate_inertia_env(const lm_params* __restrict__ P, float m, float s) {
   return I;
 }
 
+// One drive pass of a sub-step: the limb's joints eliminated against the given drive state (sat / tsat), the hub or plate solve, the contact
+// operator and the PGS, on the pass-invariant terms I - the registers substep() has just computed (first pass) or the stash's copy (second pass).
+// Out: the joint rates qdn and the free body's velocity un after the pass, and (CF) the contact impulses lamc.
+template <int MODE, int VAR, int DR, int CF>
+LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBody& F, const PassTerms& I, float dt, float kd, const float cjv[3],
+                         const bool sat[3], const float tsat[3], const float tgt[3], const float qd[3], float bn, float mu_dr,
+                         bool mp_on, float m_plate, float s_plate, float qdn[3], SV& un, float lamc[3]) {
+  const S6 Fq0 = I.Fq0, Fq1 = I.Fq1, Fq2 = I.Fq2;
+  float Ha[6] = {I.Ha[0], I.Ha[1], I.Ha[2], I.Ha[3], I.Ha[4], I.Ha[5]}, r[3];
+  const float hq[3] = {I.hq[0], I.hq[1], I.hq[2]};
+  const float Jq[3][3] = {{I.Jq0[0], I.Jq0[1], I.Jq0[2]}, {I.j12[0].x, I.j12[1].x, I.j12[2].x}, {I.j12[0].y, I.j12[1].y, I.j12[2].y}};
+  const f2 j12[3] = {I.j12[0], I.j12[1], I.j12[2]};      // (Jq[1][c] | Jq[2][c])
+  const R4* PB = I.PB;
+  const int di[3] = {0, 3, 5};
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float cj = cjv[a];
+    {
+      // The drive terms, with their rounding written out: dt x (the damping that applies) is fused into H's diagonal, the unsaturated drive
+      // torque kd (q*' - q') and the damping torque cj q' are rounded products, then two subtractions.  That is how the compiler contracted
+      // `Ha += sat ? dt cj : dt (kd + cj);  r = (sat ? tsat : kd (tgt - qd)) - cj qd - hq` while every pass sat in one loop; left to it, a pass that
+      // knows more about sat[] (the first pass on registers) is contracted differently from one that does not (k_step_w2, the persistent
+      // rollouts), and the kernels must agree bit for bit
+#pragma clang fp contract(off)
+      Ha[di[a]] = fmaf(dt, sat[a] ? cj : kd + cj, Ha[di[a]]);                  // viscous joint damping is implicit in both cases
+      const float rr = sat[a] ? tsat[a] : kd * (tgt[a] - qd[a]);
+      const float damp = cj * qd[a];
+      r[a] = (rr - damp) - hq[a];
+    }
+  }
+  float Hi[6]; inv3sym(Ha, Hi);
+  // K = Fq Hinv  (columns)
+  const S6 K0 = fma6(Hi[0], Fq0, fma6(Hi[1], Fq1, Hi[2] * Fq2));
+  const S6 K1 = fma6(Hi[1], Fq0, fma6(Hi[3], Fq1, Hi[4] * Fq2));
+  const S6 K2 = fma6(Hi[2], Fq0, fma6(Hi[4], Fq1, Hi[5] * Fq2));
+  float qdd[3], qdf[3], v0f[6], vf[3];
+  R4 T[6], X[6];
+  if (MODE == 0) {
+    // articulated hub inertia  A = sum over the quad of (Isc - K F^T): rows of pairs, upper triangle only
+    float A0[6][6]; si_to_66(I.Isc, A0);
+    float A[6][6];
+#define LM_AROW(I) { \
+      const f2 k0 = sp2(comp<I>(K0)), k1 = sp2(comp<I>(K1)), k2 = sp2(comp<I>(K2)); \
+      _Pragma("unroll") for (int jp = (I) / 2; jp < 3; jp++) { \
+        const f2 f0 = jp == 0 ? Fq0.a : jp == 1 ? Fq0.b : Fq0.c, f1 = jp == 0 ? Fq1.a : jp == 1 ? Fq1.b : Fq1.c, f2_ = jp == 0 ? Fq2.a : jp == 1 ? Fq2.b : Fq2.c; \
+        const f2 v = fma_(-k2, f2_, fma_(-k1, f1, fma_(-k0, f0, mk2(A0[I][2 * jp], A0[I][2 * jp + 1])))); \
+        if (2 * jp >= (I)) A[I][2 * jp] = quad_sum(v.x); \
+        A[I][2 * jp + 1] = quad_sum(v.y); } }
+    LM_AROW(0) LM_AROW(1) LM_AROW(2) LM_AROW(3) LM_AROW(4) LM_AROW(5)
+#undef LM_AROW
+    Chol6 Ch; chol6(A, Ch);
+    // (bias | row 0) and (row 1 | row 2) with the limb's joints eliminated:  P = PB + coefficient x K,  T_r = Jb_r - K Jq_r^T
+    const f2 cp[3] = {mk2(r[0], -Jq[0][0]), mk2(r[1], -Jq[0][1]), mk2(r[2], -Jq[0][2])};
+#define LM_PROW(I) { \
+      const f2 k0 = sp2(comp<I>(K0)), k1 = sp2(comp<I>(K1)), k2 = sp2(comp<I>(K2)); \
+      T[I].p = fma_(cp[2], k2, fma_(cp[1], k1, fma_(cp[0], k0, PB[I].p))); \
+      T[I].q = fma_(-j12[2], k2, fma_(-j12[1], k1, fma_(-j12[0], k0, PB[I].q))); \
+      X[I].p = mk2(-quad_sum(T[I].p.x), T[I].p.y); X[I].q = T[I].q; }
+    LM_PROW(0) LM_PROW(1) LM_PROW(2) LM_PROW(3) LM_PROW(4) LM_PROW(5)
+#undef LM_PROW
+    chol6_solve4(Ch, X);          // X = (a0 | B0), (B1 | B2): hub acceleration and Phi T without forming Phi
+    float t0 = r[0], t1 = r[1], t2 = r[2];
+#define LM_TROW(I) { const float a = X[I].p.x; t0 = fmaf(-comp<I>(Fq0), a, t0); t1 = fmaf(-comp<I>(Fq1), a, t1); t2 = fmaf(-comp<I>(Fq2), a, t2); }
+    LM_TROW(0) LM_TROW(1) LM_TROW(2) LM_TROW(3) LM_TROW(4) LM_TROW(5)
+#undef LM_TROW
+    qdd[0] = Hi[0] * t0 + Hi[1] * t1 + Hi[2] * t2; qdd[1] = Hi[1] * t0 + Hi[3] * t1 + Hi[4] * t2; qdd[2] = Hi[2] * t0 + Hi[4] * t1 + Hi[5] * t2;
+    const float u6[6] = {F.u.w.x, F.u.w.y, F.u.w.z, F.u.v.x, F.u.v.y, F.u.v.z};
+#pragma unroll
+    for (int i = 0; i < 6; i++) v0f[i] = fmaf(dt, X[i].p.x, u6[i]);
+  } else {
+    qdd[0] = Hi[0] * r[0] + Hi[1] * r[1] + Hi[2] * r[2]; qdd[1] = Hi[1] * r[0] + Hi[3] * r[1] + Hi[4] * r[2]; qdd[2] = Hi[2] * r[0] + Hi[4] * r[1] + Hi[5] * r[2];
+#pragma unroll
+    for (int i = 0; i < 6; i++) { v0f[i] = PB[i].p.x; T[i] = PB[i]; }
+    if (mp_on) {
+      // B = Phi' T with this env's plate mass / inertia factor, through the COM (plate_inv_apply), both halves of the four-vector layout
+      const PlateInvT<float> Q1 = plate_inv(P, m_plate, s_plate);
+      PlateInvT<f2> Q; Q.ii = bc(Q1.ii); Q.c = bc(Q1.c); Q.im = sp2(Q1.im);
+      V3P al, ac;
+      plate_inv_apply<f2>(Q, v3(T[0].p, T[1].p, T[2].p), v3(T[3].p, T[4].p, T[5].p), al, ac);
+      X[0].p = al.x; X[1].p = al.y; X[2].p = al.z; X[3].p = ac.x; X[4].p = ac.y; X[5].p = ac.z;
+      plate_inv_apply<f2>(Q, v3(T[0].q, T[1].q, T[2].q), v3(T[3].q, T[4].q, T[5].q), al, ac);
+      X[0].q = al.x; X[1].q = al.y; X[2].q = al.z; X[3].q = ac.x; X[4].q = ac.y; X[5].q = ac.z;
+    } else {
+    // B = Phi T with the plate's constant inverse inertia
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+      f2 bp = sp2(0.f), bq = sp2(0.f);
+#pragma unroll
+      for (int j = 0; j < 6; j++) { const f2 ph = sp2(P->plate_phi[6 * i + j]); bp = fma_(ph, T[j].p, bp); bq = fma_(ph, T[j].q, bq); }
+      X[i].p = bp; X[i].q = bq;
+    }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; a++) qdf[a] = fmaf(dt, qdd[a], qd[a]);
+  // contact operator
+  float Wl[6];
+  float JH[3][3];   // Jq * Hinv
+#pragma unroll
+  for (int rr = 0; rr < 3; rr++) {
+    JH[rr][0] = Jq[rr][0] * Hi[0] + Jq[rr][1] * Hi[1] + Jq[rr][2] * Hi[2];
+    JH[rr][1] = Jq[rr][0] * Hi[1] + Jq[rr][1] * Hi[3] + Jq[rr][2] * Hi[4];
+    JH[rr][2] = Jq[rr][0] * Hi[2] + Jq[rr][1] * Hi[4] + Jq[rr][2] * Hi[5];
+  }
+  Wl[0] = JH[0][0] * Jq[0][0] + JH[0][1] * Jq[0][1] + JH[0][2] * Jq[0][2];
+  Wl[1] = JH[0][0] * Jq[1][0] + JH[0][1] * Jq[1][1] + JH[0][2] * Jq[1][2];
+  Wl[2] = JH[0][0] * Jq[2][0] + JH[0][1] * Jq[2][1] + JH[0][2] * Jq[2][2];
+  Wl[3] = JH[1][0] * Jq[1][0] + JH[1][1] * Jq[1][1] + JH[1][2] * Jq[1][2];
+  Wl[4] = JH[1][0] * Jq[2][0] + JH[1][1] * Jq[2][1] + JH[1][2] * Jq[2][2];
+  Wl[5] = JH[2][0] * Jq[2][0] + JH[2][1] * Jq[2][1] + JH[2][2] * Jq[2][2];
+  // free contact-space velocity: hub / plate rows (before the joints were eliminated) on v0f, plus the joint part
+  {
+    float a = 0.f; f2 b = sp2(0.f);
+#pragma unroll
+    for (int i = 0; i < 6; i++) { a = fmaf(PB[i].p.y, v0f[i], a); b = fma_(PB[i].q, sp2(v0f[i]), b); }
+    vf[0] = a + (Jq[0][0] * qdf[0] + Jq[0][1] * qdf[1] + Jq[0][2] * qdf[2]);
+    vf[1] = b.x + (Jq[1][0] * qdf[0] + Jq[1][1] * qdf[1] + Jq[1][2] * qdf[2]);
+    vf[2] = b.y + (Jq[2][0] * qdf[0] + Jq[2][1] * qdf[1] + Jq[2][2] * qdf[2]);
+  }
+  float lam[3], w[6];
+  LM_STAMP(3);
+  PgsState S; pgs_setup(S, limb, DR ? mu_dr : P->mu, bn, vf, Wl, T, X);
+  pgs_sweeps(S, 0, P->pgs_iters);
+  pgs_finish(S, DR ? mu_dr : P->mu, X, lam, w);
+  if (CF) { lamc[0] = lam[0]; lamc[1] = lam[1]; lamc[2] = lam[2]; }
+  un = sv(v3(v0f[0] + w[0], v0f[1] + w[1], v0f[2] + w[2]), v3(v0f[3] + w[3], v0f[4] + w[4], v0f[5] + w[5]));
+#pragma unroll
+  for (int a = 0; a < 3; a++) qdn[a] = qdf[a] + JH[0][a] * lam[0] + JH[1][a] * lam[1] + JH[2][a] * lam[2];
+  if (MODE == 0) {
+#define LM_WROW(I) { qdn[0] = fmaf(-comp<I>(K0), w[I], qdn[0]); qdn[1] = fmaf(-comp<I>(K1), w[I], qdn[1]); qdn[2] = fmaf(-comp<I>(K2), w[I], qdn[2]); }
+    LM_WROW(0) LM_WROW(1) LM_WROW(2) LM_WROW(3) LM_WROW(4) LM_WROW(5)
+#undef LM_WROW
+  }
+  LM_STAMP(4);
+}
+
 // One physics sub-step of one env (4 lanes).  MODE 0: F is the robot base.  MODE 1: F is the plate, the
 // robot base is fixed at (Rb, pb).
 // CF 1 (the contact-force reporting kernels): cf[0..2] += the world-frame contact impulse on this lane's foot, cf[3] += 1 when
 // the foot is loaded (lam_n > 0), both from the impulses of the sub-step's last pass.
-template <int MODE, int VAR, int DR, int CF = 0>
+template <int MODE, int VAR, int DR, int CF = 0, int REG0 = 1>
 LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const float* tl, int limb, const Stash& St,
                     FreeBody& F, const M3& Rfix, V3 pfix, float q[3], float qd[3], const float tgt[3], float tau_acc[3], const DrPhys& X, float* cf = nullptr) {
   const float dt = P->dt, kd = DR ? X.kd : P->kd;      // DR: this env's velocity gain (the block's kd unless the kd channel drew)
@@ -437,7 +665,11 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
   const bool mp_on = DR && MODE == 1 && X.mp_on;      // a plate mass channel is on (wave-uniform): per-env plate inertia instead of plate_si / plate_phi
   const float m_plate = mp_on ? X.m_plate : 0.f, s_plate = mp_on ? X.s_plate : 0.f;
   M3 Rf = quat_to_mat(F.q.w, F.q.x, F.q.y, F.q.z);
-  float bn;
+  constexpr bool REG0_ = LM_PASS0_REG ? REG0 != 0 : false;      // first pass on registers (else: both passes read the stash back, the form before round 5)
+  // read with the sub-step's other parameters, not inside the divergent phi < 0 branch (a cache round trip on every wavefront with a penetrating
+  // foot).  Not in the kernels that keep the stash form: two more live registers cost k_step_w2 20 B of scratch
+  const float baumgarte = REG0_ ? P->baumgarte : 0.f, max_depen_vel = REG0_ ? P->max_depen_vel : 0.f;
+  float bn; PassTerms I;
   {
     M3 Rb; V3 pb; SV v0;
     if (MODE == 0) { Rb = Rf; pb = F.p; v0 = F.u; } else { Rb = Rfix; pb = pfix; v0 = sv(v3(0, 0, 0), v3(0, 0, 0)); }
@@ -515,34 +747,52 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
           for (int j = 0; j < 6; j++) Ph[i][j] = P->plate_phi[6 * i + j];
         up_free = F.u - dt * mul66(Ph, hp);
       }
-      // pass-invariant contact rows in the four-vector layout: slots 10-12 (up_free[i] | Tp0[i]), slots 13-15 (Tp1[i] | Tp2[i])
-      St.put(10, up_free.w.x, Tp0.w.x, up_free.w.y, Tp0.w.y); St.put(11, up_free.w.z, Tp0.w.z, up_free.v.x, Tp0.v.x); St.put(12, up_free.v.y, Tp0.v.y, up_free.v.z, Tp0.v.z);
-      St.put(13, Tp1.w.x, Tp2.w.x, Tp1.w.y, Tp2.w.y); St.put(14, Tp1.w.z, Tp2.w.z, Tp1.v.x, Tp2.v.x); St.put(15, Tp1.v.y, Tp2.v.y, Tp1.v.z, Tp2.v.z);
+      // pass-invariant contact rows in the four-vector layout: PB[i].p = (up_free[i] | Tp0[i]), PB[i].q = (Tp1[i] | Tp2[i])
+      if (!REG0_) {
+        St.put(10, up_free.w.x, Tp0.w.x, up_free.w.y, Tp0.w.y); St.put(11, up_free.w.z, Tp0.w.z, up_free.v.x, Tp0.v.x); St.put(12, up_free.v.y, Tp0.v.y, up_free.v.z, Tp0.v.z);
+        St.put(13, Tp1.w.x, Tp2.w.x, Tp1.w.y, Tp2.w.y); St.put(14, Tp1.w.z, Tp2.w.z, Tp1.v.x, Tp2.v.x); St.put(15, Tp1.v.y, Tp2.v.y, Tp1.v.z, Tp2.v.z);
+      } else LM_PASS_ROWS(I, up_free, Tp0, Tp1, Tp2)
     }
-    bn = (phi >= 0.f) ? phi / dt : fmaxf(P->baumgarte * phi / dt, -P->max_depen_vel);
+    bn = (phi >= 0.f) ? phi / dt : REG0_ ? fmaxf(baumgarte * phi / dt, -max_depen_vel) : fmaxf(P->baumgarte * phi / dt, -P->max_depen_vel);
     // tip linear velocity per unit generalized rate, contact coordinates
     V3 e0 = K.s1.v + cross(K.s1.w, D.x);
     V3 e1 = D.j31.v + cross(D.j31.w, D.x);
     V3 e2 = D.j32.v + cross(D.j32.w, D.x);
+    if (!REG0_) {
+      // written straight from where they were computed: these kernels' register allocation is the one they had
 #ifdef LM_WAVES2
-    stash_sv3(St, 0, D.Fq0, D.Fq1, D.Fq2, D.Isc.xz, D.Isc.yz);
+      stash_sv3(St, 0, D.Fq0, D.Fq1, D.Fq2, D.Isc.xz, D.Isc.yz);
 #else
-    stash_sv3(St, 0, D.Fq0, D.Fq1, D.Fq2);
+      stash_sv3(St, 0, D.Fq0, D.Fq1, D.Fq2);
 #endif
-    St.put(5, D.H[0], D.H[1], D.H[2], D.H[3]); St.put(6, D.H[4], D.H[5], D.hq[0], D.hq[1]);
-    // Jq = contact-coordinate tip velocity per unit joint rate: row 0 plain, rows 1 and 2 interleaved (Jq[1][c] | Jq[2][c])
-    St.put(7, D.hq[2], dot(C0, e0), dot(C0, e1), dot(C0, e2));
-    St.put(8, dot(C1, e0), dot(C2, e0), dot(C1, e1), dot(C2, e1)); St.put(9, dot(C1, e2), dot(C2, e2), 0.f, 0.f);
-    if (MODE == 0) {
-      // hub rows Jb_r = [x x C_r ; C_r] of the three contact axes and the limb's bias wrench, in the four-vector layout:
-      // slots 10-12 (fcs[i] | Jb0[i]), slots 13-15 (Jb1[i] | Jb2[i]); slots 16-18 the limb's composite inertia
-      const V3 n0 = cross(D.x, C0), n1 = cross(D.x, C1), n2 = cross(D.x, C2);
-      St.put(10, D.fcs.w.x, n0.x, D.fcs.w.y, n0.y); St.put(11, D.fcs.w.z, n0.z, D.fcs.v.x, C0.x); St.put(12, D.fcs.v.y, C0.y, D.fcs.v.z, C0.z);
-      St.put(13, n1.x, n2.x, n1.y, n2.y); St.put(14, n1.z, n2.z, C1.x, C2.x); St.put(15, C1.y, C2.y, C1.z, C2.z);
-      St.put(16, D.Isc.m, D.Isc.h.x, D.Isc.h.y, D.Isc.h.z); St.put(17, D.Isc.xx, D.Isc.yy, D.Isc.zz, D.Isc.xy);
+      St.put(5, D.H[0], D.H[1], D.H[2], D.H[3]); St.put(6, D.H[4], D.H[5], D.hq[0], D.hq[1]);
+      St.put(7, D.hq[2], dot(C0, e0), dot(C0, e1), dot(C0, e2));
+      St.put(8, dot(C1, e0), dot(C2, e0), dot(C1, e1), dot(C2, e1)); St.put(9, dot(C1, e2), dot(C2, e2), 0.f, 0.f);
+      if (MODE == 0) {
+        const V3 n0 = cross(D.x, C0), n1 = cross(D.x, C1), n2 = cross(D.x, C2);
+        St.put(10, D.fcs.w.x, n0.x, D.fcs.w.y, n0.y); St.put(11, D.fcs.w.z, n0.z, D.fcs.v.x, C0.x); St.put(12, D.fcs.v.y, C0.y, D.fcs.v.z, C0.z);
+        St.put(13, n1.x, n2.x, n1.y, n2.y); St.put(14, n1.z, n2.z, C1.x, C2.x); St.put(15, C1.y, C2.y, C1.z, C2.z);
+        St.put(16, D.Isc.m, D.Isc.h.x, D.Isc.h.y, D.Isc.h.z); St.put(17, D.Isc.xx, D.Isc.yy, D.Isc.zz, D.Isc.xy);
 #ifndef LM_WAVES2
-      St.put(18, D.Isc.xz, D.Isc.yz, 0.f, 0.f);
+        St.put(18, D.Isc.xz, D.Isc.yz, 0.f, 0.f);
 #endif
+      }
+    } else {
+      I.Fq0 = s6(D.Fq0); I.Fq1 = s6(D.Fq1); I.Fq2 = s6(D.Fq2);
+      I.Ha[0] = D.H[0]; I.Ha[1] = D.H[1]; I.Ha[2] = D.H[2]; I.Ha[3] = D.H[3]; I.Ha[4] = D.H[4]; I.Ha[5] = D.H[5];
+      I.hq[0] = D.hq[0]; I.hq[1] = D.hq[1]; I.hq[2] = D.hq[2];
+      // Jq = contact-coordinate tip velocity per unit joint rate: row 0 plain, rows 1 and 2 interleaved (Jq[1][c] | Jq[2][c])
+      I.Jq0[0] = dot(C0, e0); I.Jq0[1] = dot(C0, e1); I.Jq0[2] = dot(C0, e2);
+      I.j12[0] = mk2(dot(C1, e0), dot(C2, e0)); I.j12[1] = mk2(dot(C1, e1), dot(C2, e1)); I.j12[2] = mk2(dot(C1, e2), dot(C2, e2));
+      if (MODE == 0) {
+        // hub rows Jb_r = [x x C_r ; C_r] of the three contact axes and the limb's bias wrench, in the four-vector layout:
+        // PB[i].p = (fcs[i] | Jb0[i]), PB[i].q = (Jb1[i] | Jb2[i]); and the limb's composite inertia
+        const SV Jb0 = sv(cross(D.x, C0), C0), Jb1 = sv(cross(D.x, C1), C1), Jb2 = sv(cross(D.x, C2), C2);
+        LM_PASS_ROWS(I, D.fcs, Jb0, Jb1, Jb2)
+        I.Isc = D.Isc;
+      }
+      pin_terms<MODE>(I);
+      stash_terms<MODE>(St, I);
     }
   }
 
@@ -566,166 +816,41 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
     }
   }
   float qdn[3]; SV un; float lamc[3] = {0.f, 0.f, 0.f};
-  for (int pass = 0; pass < 2; pass++) {
-    asm volatile("" ::: "memory");          // keep the stash reloads inside the pass (no hoisting across the PGS loop)
-    S6 Fq0, Fq1, Fq2; float isc_xz = 0.f, isc_yz = 0.f;
-    {
-      const float4 t0 = St.get(0), t1 = St.get(1), t2 = St.get(2), t3 = St.get(3), t4 = St.get(4);
-      isc_xz = t4.z; isc_yz = t4.w;
-      Fq0.a = mk2(t0.x, t0.y); Fq0.b = mk2(t0.z, t0.w); Fq0.c = mk2(t1.x, t1.y);
-      Fq1.a = mk2(t1.z, t1.w); Fq1.b = mk2(t2.x, t2.y); Fq1.c = mk2(t2.z, t2.w);
-      Fq2.a = mk2(t3.x, t3.y); Fq2.b = mk2(t3.z, t3.w); Fq2.c = mk2(t4.x, t4.y);
-    }
-    const float4 h5 = St.get(5), h6 = St.get(6), h7 = St.get(7), h8 = St.get(8), h9 = St.get(9);
-    float Ha[6] = {h5.x, h5.y, h5.z, h5.w, h6.x, h6.y}, r[3];
-    const float hq[3] = {h6.z, h6.w, h7.x};
-    const float Jq[3][3] = {{h7.y, h7.z, h7.w}, {h8.x, h8.z, h9.x}, {h8.y, h8.w, h9.y}};
-    const f2 j12[3] = {mk2(h8.x, h8.y), mk2(h8.z, h8.w), mk2(h9.x, h9.y)};      // (Jq[1][c] | Jq[2][c])
-    const int di[3] = {0, 3, 5};
+  // whether a second pass is due after the first (wave-uniform): some joint of some env newly sits on its limit
+  auto second_pass_due = [&]() -> bool {
+    if (effort || (VAR != 0 && !P->pd_second_pass)) return false;
+    int any = 0;
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-      const float cj = cjv[a];
-      const float dd = sat[a] ? dt * cj : dt * (kd + cj);                  // viscous joint damping is implicit in both cases
-      const float rr = sat[a] ? tsat[a] : kd * (tgt[a] - qd[a]);
-      Ha[di[a]] += dd; r[a] = rr - cj * qd[a] - hq[a];
-    }
-    float Hi[6]; inv3sym(Ha, Hi);
-    // K = Fq Hinv  (columns)
-    const S6 K0 = fma6(Hi[0], Fq0, fma6(Hi[1], Fq1, Hi[2] * Fq2));
-    const S6 K1 = fma6(Hi[1], Fq0, fma6(Hi[3], Fq1, Hi[4] * Fq2));
-    const S6 K2 = fma6(Hi[2], Fq0, fma6(Hi[4], Fq1, Hi[5] * Fq2));
-    float qdd[3], qdf[3], v0f[6], vf[3];
-    R4 T[6], X[6];
-    // pass-invariant rows (slots 10-15): PB[i].p = (fcs[i] | Jb0[i]) or (up_free[i] | Tp0[i]),  PB[i].q = (row 1 | row 2)
-    R4 PB[6];
-    {
-      const float4 g0 = St.get(10), g1 = St.get(11), g2 = St.get(12), g3 = St.get(13), g4 = St.get(14), g5 = St.get(15);
-      PB[0].p = mk2(g0.x, g0.y); PB[1].p = mk2(g0.z, g0.w); PB[2].p = mk2(g1.x, g1.y); PB[3].p = mk2(g1.z, g1.w); PB[4].p = mk2(g2.x, g2.y); PB[5].p = mk2(g2.z, g2.w);
-      PB[0].q = mk2(g3.x, g3.y); PB[1].q = mk2(g3.z, g3.w); PB[2].q = mk2(g4.x, g4.y); PB[3].q = mk2(g4.z, g4.w); PB[4].q = mk2(g5.x, g5.y); PB[5].q = mk2(g5.z, g5.w);
-    }
-    if (MODE == 0) {
-#ifdef LM_WAVES2
-      const float4 g16 = St.get(16), g17 = St.get(17), g18 = make_float4(isc_xz, isc_yz, 0.f, 0.f);
-#else
-      const float4 g16 = St.get(16), g17 = St.get(17), g18 = St.get(18); (void)isc_xz; (void)isc_yz;
-#endif
-      SI Isc; Isc.m = g16.x; Isc.h = v3(g16.y, g16.z, g16.w); Isc.xx = g17.x; Isc.yy = g17.y; Isc.zz = g17.z; Isc.xy = g17.w; Isc.xz = g18.x; Isc.yz = g18.y;
-      // articulated hub inertia  A = sum over the quad of (Isc - K F^T): rows of pairs, upper triangle only
-      float A0[6][6]; si_to_66(Isc, A0);
-      float A[6][6];
-#define LM_AROW(I) { \
-        const f2 k0 = sp2(comp<I>(K0)), k1 = sp2(comp<I>(K1)), k2 = sp2(comp<I>(K2)); \
-        _Pragma("unroll") for (int jp = (I) / 2; jp < 3; jp++) { \
-          const f2 f0 = jp == 0 ? Fq0.a : jp == 1 ? Fq0.b : Fq0.c, f1 = jp == 0 ? Fq1.a : jp == 1 ? Fq1.b : Fq1.c, f2_ = jp == 0 ? Fq2.a : jp == 1 ? Fq2.b : Fq2.c; \
-          const f2 v = fma_(-k2, f2_, fma_(-k1, f1, fma_(-k0, f0, mk2(A0[I][2 * jp], A0[I][2 * jp + 1])))); \
-          if (2 * jp >= (I)) A[I][2 * jp] = quad_sum(v.x); \
-          A[I][2 * jp + 1] = quad_sum(v.y); } }
-      LM_AROW(0) LM_AROW(1) LM_AROW(2) LM_AROW(3) LM_AROW(4) LM_AROW(5)
-#undef LM_AROW
-      Chol6 Ch; chol6(A, Ch);
-      // (bias | row 0) and (row 1 | row 2) with the limb's joints eliminated:  P = PB + coefficient x K,  T_r = Jb_r - K Jq_r^T
-      const f2 cp[3] = {mk2(r[0], -Jq[0][0]), mk2(r[1], -Jq[0][1]), mk2(r[2], -Jq[0][2])};
-#define LM_PROW(I) { \
-        const f2 k0 = sp2(comp<I>(K0)), k1 = sp2(comp<I>(K1)), k2 = sp2(comp<I>(K2)); \
-        T[I].p = fma_(cp[2], k2, fma_(cp[1], k1, fma_(cp[0], k0, PB[I].p))); \
-        T[I].q = fma_(-j12[2], k2, fma_(-j12[1], k1, fma_(-j12[0], k0, PB[I].q))); \
-        X[I].p = mk2(-quad_sum(T[I].p.x), T[I].p.y); X[I].q = T[I].q; }
-      LM_PROW(0) LM_PROW(1) LM_PROW(2) LM_PROW(3) LM_PROW(4) LM_PROW(5)
-#undef LM_PROW
-      chol6_solve4(Ch, X);          // X = (a0 | B0), (B1 | B2): hub acceleration and Phi T without forming Phi
-      float t0 = r[0], t1 = r[1], t2 = r[2];
-#define LM_TROW(I) { const float a = X[I].p.x; t0 = fmaf(-comp<I>(Fq0), a, t0); t1 = fmaf(-comp<I>(Fq1), a, t1); t2 = fmaf(-comp<I>(Fq2), a, t2); }
-      LM_TROW(0) LM_TROW(1) LM_TROW(2) LM_TROW(3) LM_TROW(4) LM_TROW(5)
-#undef LM_TROW
-      qdd[0] = Hi[0] * t0 + Hi[1] * t1 + Hi[2] * t2; qdd[1] = Hi[1] * t0 + Hi[3] * t1 + Hi[4] * t2; qdd[2] = Hi[2] * t0 + Hi[4] * t1 + Hi[5] * t2;
-      const float u6[6] = {F.u.w.x, F.u.w.y, F.u.w.z, F.u.v.x, F.u.v.y, F.u.v.z};
-#pragma unroll
-      for (int i = 0; i < 6; i++) v0f[i] = fmaf(dt, X[i].p.x, u6[i]);
-    } else {
-      qdd[0] = Hi[0] * r[0] + Hi[1] * r[1] + Hi[2] * r[2]; qdd[1] = Hi[1] * r[0] + Hi[3] * r[1] + Hi[4] * r[2]; qdd[2] = Hi[2] * r[0] + Hi[4] * r[1] + Hi[5] * r[2];
-#pragma unroll
-      for (int i = 0; i < 6; i++) { v0f[i] = PB[i].p.x; T[i] = PB[i]; }
-      if (mp_on) {
-        // B = Phi' T with this env's plate mass / inertia factor, through the COM (plate_inv_apply), both halves of the four-vector layout
-        const PlateInvT<float> Q1 = plate_inv(P, m_plate, s_plate);
-        PlateInvT<f2> Q; Q.ii = bc(Q1.ii); Q.c = bc(Q1.c); Q.im = sp2(Q1.im);
-        V3P al, ac;
-        plate_inv_apply<f2>(Q, v3(T[0].p, T[1].p, T[2].p), v3(T[3].p, T[4].p, T[5].p), al, ac);
-        X[0].p = al.x; X[1].p = al.y; X[2].p = al.z; X[3].p = ac.x; X[4].p = ac.y; X[5].p = ac.z;
-        plate_inv_apply<f2>(Q, v3(T[0].q, T[1].q, T[2].q), v3(T[3].q, T[4].q, T[5].q), al, ac);
-        X[0].q = al.x; X[1].q = al.y; X[2].q = al.z; X[3].q = ac.x; X[4].q = ac.y; X[5].q = ac.z;
+      const float tau = kd * (tgt[a] - qdn[a]);
+      const bool hi_ = tau > tmax[a], lo_ = tau < -tmax[a];
+      if (VAR) {                             // joints already on the limit (the pre-step decision) stay there
+        const bool nw = !sat[a] && (hi_ || lo_);
+        tsat[a] = nw ? (hi_ ? tmax[a] : -tmax[a]) : tsat[a]; sat[a] = sat[a] || nw; any |= nw ? 1 : 0;
       } else {
-      // B = Phi T with the plate's constant inverse inertia
-#pragma unroll
-      for (int i = 0; i < 6; i++) {
-        f2 bp = sp2(0.f), bq = sp2(0.f);
-#pragma unroll
-        for (int j = 0; j < 6; j++) { const f2 ph = sp2(P->plate_phi[6 * i + j]); bp = fma_(ph, T[j].p, bp); bq = fma_(ph, T[j].q, bq); }
-        X[i].p = bp; X[i].q = bq;
-      }
+        sat[a] = hi_ || lo_; tsat[a] = hi_ ? tmax[a] : -tmax[a]; any |= (hi_ || lo_) ? 1 : 0;
       }
     }
-#pragma unroll
-    for (int a = 0; a < 3; a++) qdf[a] = fmaf(dt, qdd[a], qd[a]);
-    // contact operator
-    float Wl[6];
-    float JH[3][3];   // Jq * Hinv
-#pragma unroll
-    for (int rr = 0; rr < 3; rr++) {
-      JH[rr][0] = Jq[rr][0] * Hi[0] + Jq[rr][1] * Hi[1] + Jq[rr][2] * Hi[2];
-      JH[rr][1] = Jq[rr][0] * Hi[1] + Jq[rr][1] * Hi[3] + Jq[rr][2] * Hi[4];
-      JH[rr][2] = Jq[rr][0] * Hi[2] + Jq[rr][1] * Hi[4] + Jq[rr][2] * Hi[5];
-    }
-    Wl[0] = JH[0][0] * Jq[0][0] + JH[0][1] * Jq[0][1] + JH[0][2] * Jq[0][2];
-    Wl[1] = JH[0][0] * Jq[1][0] + JH[0][1] * Jq[1][1] + JH[0][2] * Jq[1][2];
-    Wl[2] = JH[0][0] * Jq[2][0] + JH[0][1] * Jq[2][1] + JH[0][2] * Jq[2][2];
-    Wl[3] = JH[1][0] * Jq[1][0] + JH[1][1] * Jq[1][1] + JH[1][2] * Jq[1][2];
-    Wl[4] = JH[1][0] * Jq[2][0] + JH[1][1] * Jq[2][1] + JH[1][2] * Jq[2][2];
-    Wl[5] = JH[2][0] * Jq[2][0] + JH[2][1] * Jq[2][1] + JH[2][2] * Jq[2][2];
-    // free contact-space velocity: hub / plate rows (before the joints were eliminated) on v0f, plus the joint part
-    {
-      float a = 0.f; f2 b = sp2(0.f);
-#pragma unroll
-      for (int i = 0; i < 6; i++) { a = fmaf(PB[i].p.y, v0f[i], a); b = fma_(PB[i].q, sp2(v0f[i]), b); }
-      vf[0] = a + (Jq[0][0] * qdf[0] + Jq[0][1] * qdf[1] + Jq[0][2] * qdf[2]);
-      vf[1] = b.x + (Jq[1][0] * qdf[0] + Jq[1][1] * qdf[1] + Jq[1][2] * qdf[2]);
-      vf[2] = b.y + (Jq[2][0] * qdf[0] + Jq[2][1] * qdf[1] + Jq[2][2] * qdf[2]);
-    }
-    float lam[3], w[6];
-    LM_STAMP(3);
-    PgsState S; pgs_setup(S, limb, DR ? mu_dr : P->mu, bn, vf, Wl, T, X);
-    pgs_sweeps(S, 0, P->pgs_iters);
-    pgs_finish(S, DR ? mu_dr : P->mu, X, lam, w);
-    if (CF) { lamc[0] = lam[0]; lamc[1] = lam[1]; lamc[2] = lam[2]; }
-    un = sv(v3(v0f[0] + w[0], v0f[1] + w[1], v0f[2] + w[2]), v3(v0f[3] + w[3], v0f[4] + w[4], v0f[5] + w[5]));
-#pragma unroll
-    for (int a = 0; a < 3; a++) qdn[a] = qdf[a] + JH[0][a] * lam[0] + JH[1][a] * lam[1] + JH[2][a] * lam[2];
-    if (MODE == 0) {
-#define LM_WROW(I) { qdn[0] = fmaf(-comp<I>(K0), w[I], qdn[0]); qdn[1] = fmaf(-comp<I>(K1), w[I], qdn[1]); qdn[2] = fmaf(-comp<I>(K2), w[I], qdn[2]); }
-      LM_WROW(0) LM_WROW(1) LM_WROW(2) LM_WROW(3) LM_WROW(4) LM_WROW(5)
-#undef LM_WROW
-    }
-    LM_STAMP(4);
-    if (pass == 0) {
-      if (effort || (VAR != 0 && !P->pd_second_pass)) break;
-      int any = 0;
-#pragma unroll
-      for (int a = 0; a < 3; a++) {
-        const float tau = kd * (tgt[a] - qdn[a]);
-        const bool hi_ = tau > tmax[a], lo_ = tau < -tmax[a];
-        if (VAR) {                             // joints already on the limit (the pre-step decision) stay there
-          const bool nw = !sat[a] && (hi_ || lo_);
-          tsat[a] = nw ? (hi_ ? tmax[a] : -tmax[a]) : tsat[a]; sat[a] = sat[a] || nw; any |= nw ? 1 : 0;
-        } else {
-          sat[a] = hi_ || lo_; tsat[a] = hi_ ? tmax[a] : -tmax[a]; any |= (hi_ || lo_) ? 1 : 0;
-        }
-      }
-      any = quad_sum_i(any);
+    any = quad_sum_i(any);
 #ifdef LM_COUNT_PASS2
-      { const bool wa = __any(any); if ((threadIdx.x & 63) == 0) { atomicAdd(&lm_dbg_pass2[0], 1u); if (wa) atomicAdd(&lm_dbg_pass2[1], 1u); } }
+    { const bool wa = __any(any); if ((threadIdx.x & 63) == 0) { atomicAdd(&lm_dbg_pass2[0], 1u); if (wa) atomicAdd(&lm_dbg_pass2[1], 1u); } }
 #endif
-      if (!__any(any)) break;                  // wave-uniform: nobody saturated
-      // envs without saturation redo the identical unsaturated solve in pass 1 (same result)
+    return __any(any);                       // wave-uniform: false when nobody saturated
+  };
+  if (!REG0_) {
+    // both passes from the stash (the form before round 5)
+    for (int pass = 0; pass < 2; pass++) {
+      unstash_terms<MODE>(St, I);
+      substep_pass<MODE, VAR, DR, CF>(P, limb, F, I, dt, kd, cjv, sat, tsat, tgt, qd, bn, mu_dr, mp_on, m_plate, s_plate, qdn, un, lamc);
+      if (pass == 0 && !second_pass_due()) break;
+    }
+  } else {
+    // first pass: on the registers just computed.  Second pass: reloaded from the stash, under a wave-uniform branch; envs without saturation
+    // redo the identical unsaturated solve in it (same result)
+    substep_pass<MODE, VAR, DR, CF>(P, limb, F, I, dt, kd, cjv, sat, tsat, tgt, qd, bn, mu_dr, mp_on, m_plate, s_plate, qdn, un, lamc);
+    if (second_pass_due()) {
+      unstash_terms<MODE>(St, I);
+      substep_pass<MODE, VAR, DR, CF>(P, limb, F, I, dt, kd, cjv, sat, tsat, tgt, qd, bn, mu_dr, mp_on, m_plate, s_plate, qdn, un, lamc);
     }
   }
 #pragma unroll

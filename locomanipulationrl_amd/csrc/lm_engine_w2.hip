@@ -15,7 +15,8 @@ __global__ void __launch_bounds__(64) LM_STEP_ATTR k_step_w2(StepArgs A) {
   LM_STEP_PROLOGUE
   // locomotion only: the plate specialisation does not live in 256 registers (measured with both in this kernel: 300 against 533 M env-steps/s on
   // the manipulation task at 65 536 envs), so manipulation and co-training engines stay on the one-wavefront kernel at every size
-  step_body<0, 0, 0>(A, P, sTab, sObs, sSt, sStash);
+  // last argument 0: both passes of a sub-step read the stash (lm_dynamics.h): in 256 registers the first pass on registers costs 40 B more scratch
+  step_body<0, 0, 0, 0, 0, 0>(A, P, sTab, sObs, sSt, sStash);
   LM_STEP_EPILOGUE
 }
 extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_w2(const StepArgs* A, int nblocks, hipStream_t s) {

@@ -12,10 +12,12 @@ struct RolloutDev {
 };
 
 // the step of the persistent kernel as a real call: its ~350 registers are then allocated separately from the policy tile's
+// (last template argument 0: both passes of a sub-step read the stash, lm_dynamics.h - on registers the first pass costs these kernels, which sit at
+// 512 registers, 130-190 B more scratch)
 LM_DEV void step_dispatch(const StepArgs& B, const lm_params* P, float* sTab, float* sObs, float* sSt, float4* sStash) {
-  if (P->variant == 0) { if (P->mode == LM_MODE_LOCO) step_body<0, 0, 0, 1>(B, P, sTab, sObs, sSt, sStash); else step_body<1, 0, 0, 1>(B, P, sTab, sObs, sSt, sStash); }
-  else if (P->variant == 1) { if (P->mode == LM_MODE_LOCO) step_body<0, 1, 0, 1>(B, P, sTab, sObs, sSt, sStash); else step_body<1, 1, 0, 1>(B, P, sTab, sObs, sSt, sStash); }
-  else { if (P->mode == LM_MODE_LOCO) step_body<0, 2, 0, 1>(B, P, sTab, sObs, sSt, sStash); else step_body<1, 2, 0, 1>(B, P, sTab, sObs, sSt, sStash); }
+  if (P->variant == 0) { if (P->mode == LM_MODE_LOCO) step_body<0, 0, 0, 1, 0, 0>(B, P, sTab, sObs, sSt, sStash); else step_body<1, 0, 0, 1, 0, 0>(B, P, sTab, sObs, sSt, sStash); }
+  else if (P->variant == 1) { if (P->mode == LM_MODE_LOCO) step_body<0, 1, 0, 1, 0, 0>(B, P, sTab, sObs, sSt, sStash); else step_body<1, 1, 0, 1, 0, 0>(B, P, sTab, sObs, sSt, sStash); }
+  else { if (P->mode == LM_MODE_LOCO) step_body<0, 2, 0, 1, 0, 0>(B, P, sTab, sObs, sSt, sStash); else step_body<1, 2, 0, 1, 0, 0>(B, P, sTab, sObs, sSt, sStash); }
 }
 
 template <int NOBS, int POLICY> struct PolicySmem { MlpSmem<NOBS> M; };
