@@ -115,6 +115,51 @@ int lm_rollout_set_episode_record(lm_rollout* r, float* record, int episode_cap)
  * after each lm_step. */
 int lm_episode_update(struct lm_engine* h, const float* rewards, const int64_t* dones, float* record, int episode_cap, void* stream);
 
+/* ---- PPO update (csrc/lm_ppo.hip): the loss and parameter gradient of one mini-batch of train/ppo.py PPO.update for the MLP policy above,
+ * and GAE.  The optimiser, the gradient-norm clip, the KL-adaptive rate and the scalers stay with the caller.
+ *
+ * Flat parameter / gradient block, fp32, torch layout (row-major (out, in)), num_obs in {64, 88}:
+ *   W1 (256, num_obs) | b1 (256) | W2 (128, 256) | b2 (128) | W3 (64, 128) | b3 (64) | Wm (12, 64) | bm (12) | Wv (1, 64) | bv (1) | log_std (12)
+ * lm_mlp_grad_param_count(num_obs) is its length (58 649 / 64 793; -1 for another width).  It is read as it stands: no packing between
+ * optimiser steps. */
+int lm_mlp_grad_param_count(int num_obs);
+
+typedef struct lm_ppo_hyper {
+  float ratio_clip;       /* rc: the ratio is clamped to [1 - rc, 1 + rc] */
+  float value_clip;       /* the value prediction moves at most this far from old_value_n */
+  float value_scale;      /* factor on the value loss */
+  float entropy_scale;    /* factor on the entropy term */
+} lm_ppo_hyper;
+
+/* With  mean, v = MLP(obs_n);  logp = sum_j [-1/2 ((a_j - mean_j) / exp(ls_j))^2 - ls_j - 1/2 ln 2 pi];  rl = logp - old_logp;  ratio = exp(rl):
+ *   loss_pi = -mean_b min(adv ratio, adv clamp(ratio, 1 - rc, 1 + rc))
+ *   vc = old_v + clamp(v - old_v, -value_clip, +value_clip);  loss_v = value_scale mean_b (ret - vc)^2
+ *   ent = sum_j (ls_j + 1/2 + 1/2 ln 2 pi);  loss = loss_pi + loss_v - entropy_scale ent;  kl = mean_b ((ratio - 1) - rl)
+ * grad [lm_mlp_grad_param_count] = d loss / d params, in the order of `params`;  stats [4] = loss_pi, loss_v, kl, ent.
+ * Inputs, device fp32 contiguous: params (16-byte aligned), obs_n [B][num_obs] (normalised and clipped by the caller; 16-byte aligned),
+ * actions [B][12], old_logp [B], old_value_n [B], adv [B], ret_n [B].  B is not padded by the caller: a ragged last tile is masked.
+ * workspace: device memory, 16-byte aligned, at least lm_mlp_ppo_grad_workspace(num_obs, B) bytes (its contents on entry do not matter).
+ * Every product runs as v_mfma_f32_16x16x4_f32 (exact fp32); no activation leaves the chip; two calls on the same inputs write the same
+ * bits (per-workgroup partial sums in the workspace, added in a fixed order by a second kernel; no atomics).
+ * Returns 0; LM_EINVAL (-1) for a null pointer, B < 1, num_obs not 64 / 88, a misaligned block, a workspace that is too small, or buffers
+ * that are not memory of the calling thread's current device; -2 for a launch failure. */
+int lm_mlp_ppo_grad(const float* params, const float* obs_n, const float* actions, const float* old_logp, const float* old_value_n,
+                    const float* adv, const float* ret_n, int B, int num_obs, const lm_ppo_hyper* hp, float* grad, float* stats,
+                    void* workspace, long long workspace_bytes, void* stream);
+/* Bytes of workspace a call of that size needs (negative: the error code of lm_mlp_ppo_grad_geometry). */
+long long lm_mlp_ppo_grad_workspace(int num_obs, int B);
+/* The sample-tile size and the number of workgroups a call of that size launches on the current device: groups = min(tiles, compute
+ * units), each workgroup looping over its tiles.  -2 without a device. */
+int lm_mlp_ppo_grad_geometry(int num_obs, int B, int* tile, int* groups);
+
+/* GAE(gamma, lambda) and returns in one launch, one lane per env, over a rollout plan's own buffers: rewards [T][N], values [T][N],
+ * dones int64 [T][N], last_value [N] -> returns [T][N], advantages [T][N].  For t = T-1 .. 0, every operation rounded once, no contraction:
+ *   nd = 1 - done;  delta = (r + (g32 next) nd) - v;  last = delta + (gl32 nd) last;  adv = last;  ret = adv + v;  next = v
+ * with g32 = (float)gamma and gl32 = (float)(gamma * lam) (the double product, rounded once): bit for bit what distributed.compute_gae
+ * computes in torch.  Returns 0, LM_EINVAL (null pointer, T < 1, N < 1) or -2. */
+int lm_gae(const float* rewards, const float* values, const int64_t* dones, const float* last_value, int T, int N, double gamma, double lam,
+           float* returns, float* advantages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

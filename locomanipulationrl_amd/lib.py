@@ -32,7 +32,8 @@ EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass
            "lm_forward_kinematics", "lm_debug_dynamics", "lm_ptr", "lm_num_envs", "lm_num_obs", "lm_set_seed", "lm_last_error", "lm_version", "lm_abi_version",
            "lm_gnn_param_count", "lm_gnn_forward", "lm_mlp_param_count", "lm_mlp_forward", "lm_mlp_param_count_obs", "lm_mlp_forward_obs",
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy",
-           "lm_rollout_set_deterministic", "lm_rollout_set_episode_record", "lm_episode_update"]
+           "lm_rollout_set_deterministic", "lm_rollout_set_episode_record", "lm_episode_update",
+           "lm_mlp_grad_param_count", "lm_mlp_ppo_grad", "lm_mlp_ppo_grad_workspace", "lm_mlp_ppo_grad_geometry", "lm_gae"]
 
 # rows of the SoA float state
 ROW = dict(base_pos=0, base_quat=3, base_lin=7, base_ang=10, q=13, qd=25, plate_pos=37, plate_quat=40, plate_lin=44,
@@ -100,6 +101,11 @@ def make_actuator_dr(ep) -> LmActuatorDr:
 # the setter families of the domain randomisation: EngineParams attribute, maker of the C struct, C entry point
 _DR_FAMILIES = (("dr_reset", make_reset_dr, "lm_set_reset_randomization"), ("dr_mass", make_mass_dr, "lm_set_mass_randomization"),
                 ("dr_actuator", make_actuator_dr, "lm_set_actuator_randomization"))
+
+
+class LmPpoHyper(C.Structure):
+    """lm_ppo_hyper (include/lm_policy.h): ratio clip, value clip, value-loss scale, entropy scale."""
+    _fields_ = [("ratio_clip", C.c_float), ("value_clip", C.c_float), ("value_scale", C.c_float), ("entropy_scale", C.c_float)]
 
 
 ABI_VERSION = 5          # LM_ABI_VERSION of include/lm_engine.h this mirror was written against
@@ -194,7 +200,7 @@ def hipcc_command(extra, out):
     # LDS stores) needs no v_accvgpr_read per element (504 of them in k_gnn_forward)
     return [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
             "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"),
-            os.path.join(_CSRC, "lm_policy.hip"), "-o", out]
+            os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), "-o", out]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -253,6 +259,11 @@ def load_library() -> C.CDLL:
     lib.lm_rollout_set_deterministic.argtypes = [vp, ip]
     lib.lm_rollout_set_episode_record.argtypes = [vp, fp, ip]
     lib.lm_episode_update.argtypes = [vp, fp, vp, fp, ip, vp]
+    lib.lm_mlp_grad_param_count.argtypes = [ip]
+    lib.lm_mlp_ppo_grad.argtypes = [fp, fp, fp, fp, fp, fp, fp, ip, ip, C.POINTER(LmPpoHyper), fp, fp, vp, C.c_longlong, vp]
+    lib.lm_mlp_ppo_grad_workspace.argtypes = [ip, ip]; lib.lm_mlp_ppo_grad_workspace.restype = C.c_longlong
+    lib.lm_mlp_ppo_grad_geometry.argtypes = [ip, ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.lm_gae.argtypes = [fp, fp, vp, fp, ip, ip, C.c_double, C.c_double, fp, fp, vp]
     lib.lm_last_error.restype = C.c_char_p
     lib.lm_version.restype = C.c_char_p
     _lib = lib

@@ -88,3 +88,112 @@ def mlp_forward_hip(obs: torch.Tensor, packed: torch.Tensor):
     if rc != 0:
         raise RuntimeError(f"lm_mlp_forward failed ({rc})")
     return mean, value
+
+
+# ------------------------------------------------------------------------------------------------ PPO update on the GPU (csrc/lm_ppo.hip)
+# names of SharedMLP's parameters in the order of the flat block of include/lm_policy.h (lm_mlp_ppo_grad)
+FLAT_ORDER = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias", "mean_layer.weight", "mean_layer.bias",
+              "value_layer.weight", "value_layer.bias", "log_std_parameter")
+
+
+def flatten_mlp_params(model: SharedMLP):
+    """{parameter name: (offset, shape)} of the flat parameter / gradient block lm_mlp_ppo_grad reads and writes, and its length
+    (= lm_mlp_grad_param_count(num_obs)).  Host arithmetic only: no library, no device."""
+    named = dict(model.named_parameters())
+    assert set(named) == set(FLAT_ORDER), sorted(named)
+    offsets, o = {}, 0
+    for name in FLAT_ORDER:
+        offsets[name] = (o, tuple(named[name].shape)); o += named[name].numel()
+    return offsets, o
+
+
+@torch.no_grad()
+def bind_flat_params(model: SharedMLP):
+    """Move the model's parameters into ONE flat fp32 buffer in the header's order and their .grads into a second one: every parameter
+    (and its .grad) becomes a view, so the kernel reads the weights the optimiser has just stepped and writes the gradient the optimiser
+    reads next, with no copy in between.  state_dict() / load_state_dict() are unaffected (they copy values in place).  Returns
+    (flat, grad_flat, offsets)."""
+    offsets, total = flatten_mlp_params(model)
+    named = dict(model.named_parameters())
+    dev = model.log_std_parameter.device
+    flat = torch.empty(total, device=dev, dtype=torch.float32); gflat = torch.zeros(total, device=dev, dtype=torch.float32)
+    for name, (o, shape) in offsets.items():
+        p = named[name]
+        flat[o:o + p.numel()].copy_(p.detach().reshape(-1))
+        p.data = flat[o:o + p.numel()].view(shape)
+        p.grad = gflat[o:o + p.numel()].view(shape)
+    return flat, gflat, offsets
+
+
+def ppo_grad_geometry(num_obs: int, B: int, device=None):
+    """(tile, groups): the sample-tile size and the number of workgroups lm_mlp_ppo_grad launches for B samples on `device`."""
+    from ..lib import load_library
+    lib = load_library(); tile, groups = C.c_int(0), C.c_int(0)
+    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+        rc = lib.lm_mlp_ppo_grad_geometry(int(num_obs), int(B), C.byref(tile), C.byref(groups))
+    if rc != 0:
+        raise RuntimeError(f"lm_mlp_ppo_grad_geometry failed ({rc}): {lib.lm_last_error().decode()}")
+    return tile.value, groups.value
+
+
+def ppo_grad_workspace(num_obs: int, B: int, device):
+    """A workspace tensor of the size lm_mlp_ppo_grad needs for B samples (its contents never matter)."""
+    from ..lib import load_library
+    lib = load_library()
+    with torch.cuda.device(device):
+        nbytes = lib.lm_mlp_ppo_grad_workspace(int(num_obs), int(B))
+    if nbytes <= 0:
+        raise RuntimeError(f"lm_mlp_ppo_grad_workspace failed ({nbytes}): {lib.lm_last_error().decode()}")
+    return torch.empty(nbytes // 4, device=device, dtype=torch.float32)
+
+
+def mlp_ppo_grad(params, obs_n, actions, old_logp, old_value_n, adv, ret_n, ratio_clip=0.2, value_clip=0.2, value_scale=1.0, entropy_scale=0.0,
+                 grad=None, stats=None, workspace=None):
+    """lm_mlp_ppo_grad: loss and gradient of one PPO mini-batch for the flat SharedMLP parameter block `params` (order: FLAT_ORDER).
+    Returns (grad, stats) with stats = [loss_pi, loss_v, kl, entropy term]; `grad`, `stats` and `workspace` are allocated when not given.
+    No fallback: a missing kernel or a refused call raises."""
+    from ..lib import load_library, LmPpoHyper
+    lib = load_library()
+    B, nobs = int(obs_n.shape[0]), int(obs_n.shape[1])
+    dev = params.device
+    if dev.type != "cuda":
+        raise RuntimeError("mlp_ppo_grad runs on a HIP device only (no CPU fallback)")
+    f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+    obs_n, actions, old_logp, old_value_n, adv, ret_n = (f32(t) for t in (obs_n, actions, old_logp, old_value_n, adv, ret_n))
+    for t, shape in ((obs_n, (B, nobs)), (actions, (B, 12)), (old_logp, (B,)), (old_value_n, (B,)), (adv, (B,)), (ret_n, (B,))):
+        assert t.device == dev and tuple(t.shape) == shape, (t.device, tuple(t.shape), shape)
+    assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == lib.lm_mlp_grad_param_count(nobs), (params.numel(), nobs)
+    if grad is None: grad = torch.empty_like(params)
+    if stats is None: stats = torch.empty(4, device=dev, dtype=torch.float32)
+    if workspace is None: workspace = ppo_grad_workspace(nobs, B, dev)
+    assert grad.is_contiguous() and grad.numel() == params.numel() and stats.numel() == 4 and workspace.device == dev
+    hp = LmPpoHyper(float(ratio_clip), float(value_clip), float(value_scale), float(entropy_scale))
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):            # the kernels launch on the calling thread's current device
+        rc = lib.lm_mlp_ppo_grad(p(params), p(obs_n), p(actions), p(old_logp), p(old_value_n), p(adv), p(ret_n), B, nobs, C.byref(hp), p(grad), p(stats),
+                                 p(workspace), workspace.numel() * workspace.element_size(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"lm_mlp_ppo_grad failed ({rc}): {lib.lm_last_error().decode()}")
+    return grad, stats
+
+
+def gae(rewards, values, dones, last_value, gamma: float = 0.99, lam: float = 0.95):
+    """lm_gae: (returns, advantages) of distributed.compute_gae, bit for bit, in one launch.  rewards / values (T, N) float32, dones (T, N)
+    int64 (the rollout plan's own buffer), last_value (N,)."""
+    from ..lib import load_library
+    lib = load_library()
+    dev = rewards.device
+    if dev.type != "cuda":
+        raise RuntimeError("gae runs on a HIP device only (distributed.compute_gae is the torch path)")
+    T, N = rewards.shape
+    assert dones.dtype == torch.int64 and tuple(dones.shape) == (T, N) and tuple(values.shape) == (T, N) and last_value.numel() == N
+    rewards, values, dones, last_value = rewards.contiguous(), values.contiguous(), dones.contiguous(), last_value.contiguous()
+    assert rewards.dtype == values.dtype == last_value.dtype == torch.float32
+    ret = torch.empty((T, N), device=dev, dtype=torch.float32); adv = torch.empty((T, N), device=dev, dtype=torch.float32)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        rc = lib.lm_gae(p(rewards), p(values), p(dones), p(last_value), int(T), int(N), float(gamma), float(lam), p(ret), p(adv),
+                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"lm_gae failed ({rc}): {lib.lm_last_error().decode()}")
+    return ret, adv

@@ -6,7 +6,8 @@ entropy scale 0, value scale 1, RunningStandardScaler on observations and values
 skrl itself is third-party and not installed here; this trainer exists so that the engine can be accepted
 *behaviourally* (the task's success rate rises under the reference's PPO recipe) and to exercise the multi-GPU
 exchange of SURVEY 8(e): rollout returns / advantages are all-gathered over RCCL for global advantage normalisation and
-the gradients are all-reduced.  Rollouts use the matrix-core policy forward (csrc/lm_policy.hip); updates use autograd.
+the gradients are all-reduced.  Rollouts use the matrix-core policy forward (csrc/lm_policy.hip); updates use autograd, or - opt-in, MLP
+only: PPO(hip_update=True) - the fused loss-gradient kernel and the GAE kernel of csrc/lm_ppo.hip (the GNN keeps autograd).
 """
 from __future__ import annotations
 
@@ -55,12 +56,47 @@ class RunningStandardScaler:
         return torch.clamp((x - mean) / (std + self.eps), -self.clip, self.clip)
 
 
+def gaussian_logp(mean, log_std, act):
+    return (-0.5 * ((act - mean) / log_std.exp()) ** 2 - log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
+
+
+def ppo_loss(model_outputs, act, old_logp, old_val_n, adv, ret_n, rclip, vclip, vscale, escale):
+    """The loss of one PPO mini-batch (skrl PPO._update with clipped predictions): model_outputs = (mean, log_std, v) of the model on the
+    normalised observations.  Returns (loss, loss_pi, loss_v, kl, ent); kl carries no gradient.  Dtype-agnostic: update() calls it in
+    float32, the tests of the HIP update in float64 as their reference."""
+    mean, log_std, v = model_outputs
+    logp = gaussian_logp(mean, log_std, act)
+    ratio_log = logp - old_logp
+    with torch.no_grad():
+        kl = ((ratio_log.exp() - 1) - ratio_log).mean()
+    ratio = ratio_log.exp()
+    surr = torch.min(adv * ratio, adv * ratio.clamp(1 - rclip, 1 + rclip))
+    v = v.squeeze(-1); v = old_val_n + (v - old_val_n).clamp(-vclip, vclip)
+    loss_pi = -surr.mean(); loss_v = vscale * torch.nn.functional.mse_loss(ret_n, v)
+    ent = (log_std + 0.5 + 0.5 * math.log(2 * math.pi)).sum()
+    loss = loss_pi + loss_v - escale * ent
+    return loss, loss_pi, loss_v, kl, ent
+
+
 class PPO:
     def __init__(self, env, model, rollouts=48, learning_epochs=5, mini_batches=1, gamma=0.99, lam=0.95, lr=3e-4, kl_threshold=0.012,
                  grad_norm_clip=1.0, ratio_clip=0.2, value_clip=0.2, value_loss_scale=1.0, entropy_loss_scale=0.0, hip_inference=True,
-                 fused_rollout=True, freeze_obs_scaler=False, max_lr=1e-2, min_log_std=None):
+                 fused_rollout=True, freeze_obs_scaler=False, max_lr=1e-2, min_log_std=None, hip_update=False):
         self.env, self.model = env, model
         self.dev = next(model.parameters()).device
+        self.hip_update = bool(hip_update)
+        if self.hip_update:
+            # no CPU fallback and no quiet autograd path, as in lib.Engine: say why and stop
+            n_in = int(env.observation_space.shape[0])
+            if type(model).__name__ != "SharedMLP":
+                raise ValueError(f"hip_update=True: the fused PPO gradient kernel is built for SharedMLP, not {type(model).__name__} (the GNN keeps the torch update)")
+            if self.dev.type != "cuda" or not torch.cuda.is_available():
+                raise ValueError(f"hip_update=True needs the model on a HIP device, not {self.dev} (the kernel has no CPU fallback)")
+            if n_in not in (64, 88):
+                raise ValueError(f"hip_update=True: the kernel is built for 64- and 88-wide observations, not {n_in}")
+            from ..policies.mlp_model import bind_flat_params
+            self._flat, self._gflat, self._offsets = bind_flat_params(model)      # parameters and .grads become views into two flat buffers
+            self._ppo_stats = torch.zeros(4, device=self.dev); self._ws = {}
         self.N = env.num_envs
         self.T, self.epochs, self.mb = rollouts, learning_epochs, mini_batches
         self.gamma, self.lam, self.lr, self.kl_thr = gamma, lam, lr, kl_threshold
@@ -100,9 +136,7 @@ class PPO:
                 mean, log_std, v = self.model(self.obs_scaler(obs_raw))
             return mean, log_std.detach(), self.val_scaler(v, inverse=True).squeeze(-1)
 
-    @staticmethod
-    def _logp(mean, log_std, act):
-        return (-0.5 * ((act - mean) / log_std.exp()) ** 2 - log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
+    _logp = staticmethod(gaussian_logp)
 
     # ------------------------------------------------------------------ one iteration = T env steps + update
     def collect(self, obs_raw):
@@ -126,7 +160,12 @@ class PPO:
         return obs_raw, last_value, extras
 
     def update(self, last_value) -> Dict[str, float]:
-        ret, adv = D.compute_gae(self.b_rew, self.b_val, self.b_done, last_value, self.gamma, self.lam)
+        if self.hip_update:      # one launch over the plan's own buffers (int64 dones), bit for bit compute_gae
+            from ..policies.mlp_model import gae
+            dones = self.rollout.dones if self.rollout is not None else self.b_done.long()
+            ret, adv = gae(self.b_rew, self.b_val, dones, last_value, self.gamma, self.lam)
+        else:
+            ret, adv = D.compute_gae(self.b_rew, self.b_val, self.b_done, last_value, self.gamma, self.lam)
         g_ret, g_adv = D.all_gather_rollout(ret, adv)                 # RCCL all-gather over xGMI when world > 1
         adv = (adv - g_adv.mean()) / (g_adv.std() + 1e-8)             # global advantage normalisation
         obs, act = self.b_obs.reshape(-1, self.n_obs), self.b_act.reshape(-1, 12)
@@ -136,29 +175,31 @@ class PPO:
         self.val_scaler.update(ret.unsqueeze(-1))      # preprocessors train on the first epoch's data
         obs_n = self.obs_scaler(obs); ret_n = self.val_scaler(ret.unsqueeze(-1)).squeeze(-1); old_val_n = self.val_scaler(old_val.unsqueeze(-1)).squeeze(-1)
         n = obs.shape[0]; stats = {}
+        # what the mini-batches below are cut from (references, no copies): read by the tests of the HIP update
+        self.last_batch = {"obs_n": obs_n, "act": act, "old_logp": old_logp, "old_val_n": old_val_n, "adv": adv, "ret_n": ret_n, "ret": ret}
         for epoch in range(self.epochs):
             perm = torch.randperm(n, device=self.dev) if self.mb > 1 else None
             kls = []
             for i in range(self.mb):
                 idx = slice(None) if perm is None else perm[i * n // self.mb:(i + 1) * n // self.mb]
-                mean, log_std, v = self.model(obs_n[idx])
-                logp = self._logp(mean, log_std, act[idx])
-                ratio_log = logp - old_logp[idx]
-                with torch.no_grad():
-                    kls.append(((ratio_log.exp() - 1) - ratio_log).mean())
-                ratio = ratio_log.exp()
-                surr = torch.min(adv[idx] * ratio, adv[idx] * ratio.clamp(1 - self.rclip, 1 + self.rclip))
-                v = v.squeeze(-1); v = old_val_n[idx] + (v - old_val_n[idx]).clamp(-self.vclip, self.vclip)
-                loss_pi = -surr.mean(); loss_v = self.vscale * torch.nn.functional.mse_loss(ret_n[idx], v)
-                ent = (log_std + 0.5 + 0.5 * math.log(2 * math.pi)).sum()
-                loss = loss_pi + loss_v - self.escale * ent
-                self.opt.zero_grad(set_to_none=True); loss.backward()
-                if self.world > 1:
-                    flat = torch.cat([p.grad.reshape(-1) for p in self.model.parameters() if p.grad is not None])
-                    dist.all_reduce(flat); flat /= self.world; o = 0
-                    for p in self.model.parameters():
-                        if p.grad is not None:
-                            p.grad.copy_(flat[o:o + p.numel()].view_as(p)); o += p.numel()
+                if self.hip_update:
+                    # loss and gradient of the mini-batch in one fused launch (+ its reduction) straight into the flat .grad buffer; a permuted
+                    # mini-batch is gathered with torch and handed over contiguous
+                    self._hip_grad(*(t[idx] for t in (obs_n, act, old_logp, old_val_n, adv, ret_n)))
+                    st = self._ppo_stats.clone(); loss_pi, loss_v = st[0], st[1]; kls.append(st[2])
+                    if self.world > 1:
+                        dist.all_reduce(self._gflat); self._gflat /= self.world
+                else:
+                    loss, loss_pi, loss_v, kl_mb, _ = ppo_loss(self.model(obs_n[idx]), act[idx], old_logp[idx], old_val_n[idx], adv[idx], ret_n[idx],
+                                                               self.rclip, self.vclip, self.vscale, self.escale)
+                    kls.append(kl_mb)
+                    self.opt.zero_grad(set_to_none=True); loss.backward()
+                    if self.world > 1:
+                        flat = torch.cat([p.grad.reshape(-1) for p in self.model.parameters() if p.grad is not None])
+                        dist.all_reduce(flat); flat /= self.world; o = 0
+                        for p in self.model.parameters():
+                            if p.grad is not None:
+                                p.grad.copy_(flat[o:o + p.numel()].view_as(p)); o += p.numel()
                 torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.gclip)
                 self.opt.step()
                 if self.min_log_std is not None:
@@ -173,6 +214,15 @@ class PPO:
             for gp in self.opt.param_groups: gp["lr"] = self.lr
             stats = {"kl": kl, "loss_pi": float(loss_pi), "loss_v": float(loss_v), "lr": self.lr}
         return stats
+
+    def _hip_grad(self, obs_n, act, old_logp, old_val_n, adv, ret_n):
+        """lm_mlp_ppo_grad on one mini-batch: fills the flat gradient buffer (the parameters' .grad views) and self._ppo_stats."""
+        from ..policies.mlp_model import mlp_ppo_grad, ppo_grad_workspace
+        B = int(obs_n.shape[0])
+        if B not in self._ws:
+            self._ws[B] = ppo_grad_workspace(self.n_obs, B, self.dev)
+        mlp_ppo_grad(self._flat, obs_n, act, old_logp, old_val_n, adv, ret_n, self.rclip, self.vclip, self.vscale, self.escale,
+                     grad=self._gflat, stats=self._ppo_stats, workspace=self._ws[B])
 
     # ------------------------------------------------------------------ checkpoints (what the reference's agents write as best_agent.pt: policy,
     # value head, optimiser and both preprocessors; tools/eval_policy.py and train/evaluate.py read them back)
