@@ -21,7 +21,8 @@ int lm_gnn_param_count(void);
 
 /* obs: device float [batch][64] (the env's observation layout, quadruped_pose_control.py:358-371);
  * params: device float [lm_gnn_param_count()]; mean: device float [batch][12] (node order = dof1 a1..a4, dof2 a1..a4,
- * dof3 a1..a4); value: device float [batch].  Returns 0, -1 (bad argument) or -2 (launch failure). */
+ * dof3 a1..a4); value: device float [batch].  Returns 0, -1 (bad argument) or -2 (launch failure).
+ * obs and params must be 16-byte aligned (both are read with 16-byte loads): -1 otherwise, nothing is launched. */
 int lm_gnn_forward(const float* obs, int batch, const float* params, float* mean, float* value, void* stream);
 
 /* MLP policy of the locomotion / manipulation scripts (scripts/skrl_ppo_locomotion.py:30-40: shared trunk
@@ -35,7 +36,8 @@ int lm_gnn_forward(const float* obs, int batch, const float* params, float* mean
 int lm_mlp_param_count(void);
 int lm_mlp_forward(const float* obs, int batch, const float* params, float* mean, float* value, void* stream);
 /* The same network on the 88-wide observation of the custom-controller tasks (…custom_controller.py:432-455) or the 64-wide one:
- * num_obs in {64, 88}; the packed block is  mean num_obs | 1/std num_obs | clip (+3 pad) | W1q 256 x (num_obs padded to a multiple of 32) | ... as above. */
+ * num_obs in {64, 88}; the packed block is  mean num_obs | 1/std num_obs | clip (+3 pad) | W1q 256 x (num_obs padded to a multiple of 32) | ... as above.
+ * obs and params must be 16-byte aligned, as for lm_gnn_forward: -1 otherwise (and for another num_obs), nothing is launched. */
 int lm_mlp_param_count_obs(int num_obs);
 int lm_mlp_forward_obs(const float* obs, int batch, int num_obs, const float* params, float* mean, float* value, void* stream);
 
@@ -58,7 +60,8 @@ int lm_sample_actions(const float* mean, const float* log_std, const int64_t* cn
  *                      (88-wide observations: MLP policy only)
  *   actions [T][N][12], logp [T][N], values [T+1][N] (value head output; values[T] bootstraps), rewards [T][N], dones int64 [T][N],
  *   extras [T][LM_NUM_EXTRAS] (may be NULL)
- *   policy_params / log_std: device blocks read at run time (update them in place between runs) */
+ *   policy_params / log_std: device blocks read at run time (update them in place between runs)
+ * policy_params and obs must be 16-byte aligned (16-byte loads, both policies): LM_EINVAL (-1) otherwise, no plan is made. */
 int lm_rollout_create(lm_rollout** out, struct lm_engine* env, int policy, const float* policy_params, const float* log_std, int T,
                       uint32_t noise_seed, float* obs, float* actions, float* logp, float* values, float* rewards, int64_t* dones,
                       float* extras);
