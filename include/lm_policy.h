@@ -163,6 +163,29 @@ int lm_mlp_ppo_grad_geometry(int num_obs, int B, int* tile, int* groups);
 int lm_gae(const float* rewards, const float* values, const int64_t* dones, const float* last_value, int T, int N, double gamma, double lam,
            float* returns, float* advantages, void* stream);
 
+/* ---- PPO update for the GNN policy (csrc/lm_gnn_ppo.hip): lm_mlp_ppo_grad with the network swapped (same loss, same lm_ppo_hyper, same
+ * stats, same determinism and return codes; 64-wide observations only, as lm_gnn_forward).
+ *
+ * Flat parameter / gradient block, fp32, torch layout, in the order of the packed block of lm_gnn_param_count with the scaler rows left out
+ * and log_std appended:
+ *   input_layer1.weight (32,16) .bias (32) | input_layer2.weight (32,4) .bias (32) |
+ *   3 x { linear1.weight (32,64) .bias (32) | linear2.weight (32,32) .bias (32) } |
+ *   action_layer.weight (32) .bias (1) | value action_layer.weight (32) .bias (1) | log_std (12)
+ * lm_gnn_grad_param_count() is its length (10 190).  It is read as it stands: no packing between optimiser steps.
+ * mean, v = GraphPolicy(obs_n): the feature gather of create_features happens inside the kernel (columns 0..15 to node 0; columns 16 + idx,
+ * 28 + idx, 40 + idx, 52 + idx with idx = 0 1 2 3 4 6 8 10 5 7 9 11 to the joint nodes 1..12; mean k is node k + 1).
+ * Max aggregation: an exact tie among the messages into a node splits the gradient evenly among the tied edges (autograd's amax); an exact
+ * tie in the value head's max over the nodes sends it to the lowest node index.
+ * Inputs, workspace, grad and stats as for lm_mlp_ppo_grad.  Returns 0; LM_EINVAL (-1) for a null pointer, B < 1, a misaligned block, a
+ * workspace that is too small (nothing is launched, nothing written), or buffers that are not memory of the calling thread's current device;
+ * -2 for a launch failure. */
+int lm_gnn_grad_param_count(void);
+int lm_gnn_ppo_grad(const float* params, const float* obs_n, const float* actions, const float* old_logp, const float* old_value_n,
+                    const float* adv, const float* ret_n, int B, const lm_ppo_hyper* hp, float* grad, float* stats, void* workspace,
+                    long long workspace_bytes, void* stream);
+long long lm_gnn_ppo_grad_workspace(int B);
+int lm_gnn_ppo_grad_geometry(int B, int* tile, int* groups);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,3 +147,91 @@ class GraphPolicy(nn.Module):
 
     def refresh(self, device=None, obs_mean=None, obs_var=None, eps=1e-8, clip=5.0):
         self._packed = pack_gnn_params(self.net, self.mean_layer, self.value_layer, obs_mean, obs_var, eps, clip).to(device or self.log_std_parameter.device)
+
+
+# ------------------------------------------------------------------------------------------------ PPO update on the GPU (csrc/lm_gnn_ppo.hip)
+# names of GraphPolicy's parameters in the order of the flat block of include/lm_policy.h (lm_gnn_ppo_grad)
+GNN_FLAT_ORDER = ("net.input_layer1.weight", "net.input_layer1.bias", "net.input_layer2.weight", "net.input_layer2.bias") + \
+    tuple(f"net.graph_layer{l}.{lin}.{wb}" for l in (1, 2, 3) for lin in ("linear1", "linear2") for wb in ("weight", "bias")) + \
+    ("mean_layer.action_layer.weight", "mean_layer.action_layer.bias", "value_layer.action_layer.weight", "value_layer.action_layer.bias",
+     "log_std_parameter")
+
+
+def flatten_gnn_params(model: GraphPolicy):
+    """{parameter name: (offset, shape)} of the flat parameter / gradient block lm_gnn_ppo_grad reads and writes, and its length
+    (= lm_gnn_grad_param_count()).  Host arithmetic only: no library, no device."""
+    named = dict(model.named_parameters())
+    assert set(named) == set(GNN_FLAT_ORDER), sorted(named)
+    offsets, o = {}, 0
+    for name in GNN_FLAT_ORDER:
+        offsets[name] = (o, tuple(named[name].shape)); o += named[name].numel()
+    return offsets, o
+
+
+@torch.no_grad()
+def bind_gnn_flat_params(model: GraphPolicy):
+    """Move the model's parameters into ONE flat fp32 buffer in the header's order and their .grads into a second one (every parameter and
+    its .grad becomes a view), as mlp_model.bind_flat_params does for the MLP.  state_dict() / load_state_dict() and refresh() are
+    unaffected.  Returns (flat, grad_flat, offsets)."""
+    offsets, total = flatten_gnn_params(model)
+    named = dict(model.named_parameters())
+    dev = model.log_std_parameter.device
+    flat = torch.empty(total, device=dev, dtype=torch.float32); gflat = torch.zeros(total, device=dev, dtype=torch.float32)
+    for name, (o, shape) in offsets.items():
+        p = named[name]
+        flat[o:o + p.numel()].copy_(p.detach().reshape(-1))
+        p.data = flat[o:o + p.numel()].view(shape)
+        p.grad = gflat[o:o + p.numel()].view(shape)
+    return flat, gflat, offsets
+
+
+def gnn_ppo_grad_geometry(B: int, device=None):
+    """(tile, groups): the sample-tile size and the number of workgroups lm_gnn_ppo_grad launches for B samples on `device`."""
+    from ..lib import load_library
+    lib = load_library(); tile, groups = C.c_int(0), C.c_int(0)
+    with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
+        rc = lib.lm_gnn_ppo_grad_geometry(int(B), C.byref(tile), C.byref(groups))
+    if rc != 0:
+        raise RuntimeError(f"lm_gnn_ppo_grad_geometry failed ({rc}): {lib.lm_last_error().decode()}")
+    return tile.value, groups.value
+
+
+def gnn_ppo_grad_workspace(B: int, device):
+    """A workspace tensor of the size lm_gnn_ppo_grad needs for B samples (its contents never matter)."""
+    from ..lib import load_library
+    lib = load_library()
+    with torch.cuda.device(device):
+        nbytes = lib.lm_gnn_ppo_grad_workspace(int(B))
+    if nbytes <= 0:
+        raise RuntimeError(f"lm_gnn_ppo_grad_workspace failed ({nbytes}): {lib.lm_last_error().decode()}")
+    return torch.empty(nbytes // 4, device=device, dtype=torch.float32)
+
+
+def gnn_ppo_grad(params, obs_n, actions, old_logp, old_value_n, adv, ret_n, ratio_clip=0.2, value_clip=0.2, value_scale=1.0, entropy_scale=0.0,
+                 grad=None, stats=None, workspace=None):
+    """lm_gnn_ppo_grad: loss and gradient of one PPO mini-batch for the flat GraphPolicy parameter block `params` (order: GNN_FLAT_ORDER).
+    Returns (grad, stats) with stats = [loss_pi, loss_v, kl, entropy term]; `grad`, `stats` and `workspace` are allocated when not given.
+    No fallback: a missing kernel or a refused call raises."""
+    from ..lib import load_library, LmPpoHyper
+    lib = load_library()
+    B = int(obs_n.shape[0])
+    dev = params.device
+    if dev.type != "cuda":
+        raise RuntimeError("gnn_ppo_grad runs on a HIP device only (no CPU fallback)")
+    f32 = lambda t: t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+    obs_n, actions, old_logp, old_value_n, adv, ret_n = (f32(t) for t in (obs_n, actions, old_logp, old_value_n, adv, ret_n))
+    for t, shape in ((obs_n, (B, 64)), (actions, (B, 12)), (old_logp, (B,)), (old_value_n, (B,)), (adv, (B,)), (ret_n, (B,))):
+        assert t.device == dev and tuple(t.shape) == shape, (t.device, tuple(t.shape), shape)
+    assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == lib.lm_gnn_grad_param_count(), params.numel()
+    if grad is None: grad = torch.empty_like(params)
+    if stats is None: stats = torch.empty(4, device=dev, dtype=torch.float32)
+    if workspace is None: workspace = gnn_ppo_grad_workspace(B, dev)
+    assert grad.is_contiguous() and grad.numel() == params.numel() and stats.numel() == 4 and workspace.device == dev
+    hp = LmPpoHyper(float(ratio_clip), float(value_clip), float(value_scale), float(entropy_scale))
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):            # the kernels launch on the calling thread's current device
+        rc = lib.lm_gnn_ppo_grad(p(params), p(obs_n), p(actions), p(old_logp), p(old_value_n), p(adv), p(ret_n), B, C.byref(hp), p(grad), p(stats),
+                                 p(workspace), workspace.numel() * workspace.element_size(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"lm_gnn_ppo_grad failed ({rc}): {lib.lm_last_error().decode()}")
+    return grad, stats

@@ -6,8 +6,9 @@ entropy scale 0, value scale 1, RunningStandardScaler on observations and values
 skrl itself is third-party and not installed here; this trainer exists so that the engine can be accepted
 *behaviourally* (the task's success rate rises under the reference's PPO recipe) and to exercise the multi-GPU
 exchange of SURVEY 8(e): rollout returns / advantages are all-gathered over RCCL for global advantage normalisation and
-the gradients are all-reduced.  Rollouts use the matrix-core policy forward (csrc/lm_policy.hip); updates use autograd, or - opt-in, MLP
-only: PPO(hip_update=True) - the fused loss-gradient kernel and the GAE kernel of csrc/lm_ppo.hip (the GNN keeps autograd).
+the gradients are all-reduced.  Rollouts use the matrix-core policy forward (csrc/lm_policy.hip); updates use autograd, or - opt-in - the
+fused loss-gradient kernels and the GAE kernel: PPO(hip_update=True) for the SharedMLP (csrc/lm_ppo.hip),
+PPO(gnn_hip_update=True) for the GraphPolicy (csrc/lm_gnn_ppo.hip).
 """
 from __future__ import annotations
 
@@ -81,7 +82,7 @@ def ppo_loss(model_outputs, act, old_logp, old_val_n, adv, ret_n, rclip, vclip, 
 class PPO:
     def __init__(self, env, model, rollouts=48, learning_epochs=5, mini_batches=1, gamma=0.99, lam=0.95, lr=3e-4, kl_threshold=0.012,
                  grad_norm_clip=1.0, ratio_clip=0.2, value_clip=0.2, value_loss_scale=1.0, entropy_loss_scale=0.0, hip_inference=True,
-                 fused_rollout=True, freeze_obs_scaler=False, max_lr=1e-2, min_log_std=None, hip_update=False):
+                 fused_rollout=True, freeze_obs_scaler=False, max_lr=1e-2, min_log_std=None, hip_update=False, gnn_hip_update=False):
         self.env, self.model = env, model
         self.dev = next(model.parameters()).device
         self.hip_update = bool(hip_update)
@@ -89,7 +90,7 @@ class PPO:
             # no CPU fallback and no quiet autograd path, as in lib.Engine: say why and stop
             n_in = int(env.observation_space.shape[0])
             if type(model).__name__ != "SharedMLP":
-                raise ValueError(f"hip_update=True: the fused PPO gradient kernel is built for SharedMLP, not {type(model).__name__} (the GNN keeps the torch update)")
+                raise ValueError(f"hip_update=True: the fused PPO gradient kernel is built for SharedMLP, not {type(model).__name__} (a GraphPolicy's fused update is gnn_hip_update=True)")
             if self.dev.type != "cuda" or not torch.cuda.is_available():
                 raise ValueError(f"hip_update=True needs the model on a HIP device, not {self.dev} (the kernel has no CPU fallback)")
             if n_in not in (64, 88):
@@ -97,6 +98,21 @@ class PPO:
             from ..policies.mlp_model import bind_flat_params
             self._flat, self._gflat, self._offsets = bind_flat_params(model)      # parameters and .grads become views into two flat buffers
             self._ppo_stats = torch.zeros(4, device=self.dev); self._ws = {}
+        self.gnn_hip_update = bool(gnn_hip_update)
+        if self.gnn_hip_update:
+            n_in = int(env.observation_space.shape[0])
+            if self.hip_update:
+                raise ValueError("gnn_hip_update=True and hip_update=True: one model, one fused update (hip_update is the SharedMLP's, gnn_hip_update the GraphPolicy's)")
+            if type(model).__name__ != "GraphPolicy":
+                raise ValueError(f"gnn_hip_update=True: the fused GNN gradient kernel is built for GraphPolicy, not {type(model).__name__} (hip_update=True is the SharedMLP's)")
+            if self.dev.type != "cuda" or not torch.cuda.is_available():
+                raise ValueError(f"gnn_hip_update=True needs the model on a HIP device, not {self.dev} (the kernel has no CPU fallback)")
+            if n_in != 64:
+                raise ValueError(f"gnn_hip_update=True: the GNN reads the 64-wide observation layout, not {n_in}")
+            from ..policies.graph_model import bind_gnn_flat_params
+            self._flat, self._gflat, self._offsets = bind_gnn_flat_params(model)      # parameters and .grads become views into two flat buffers
+            self._ppo_stats = torch.zeros(4, device=self.dev); self._ws = {}
+        self._fused_update = self.hip_update or self.gnn_hip_update
         self.N = env.num_envs
         self.T, self.epochs, self.mb = rollouts, learning_epochs, mini_batches
         self.gamma, self.lam, self.lr, self.kl_thr = gamma, lam, lr, kl_threshold
@@ -160,7 +176,7 @@ class PPO:
         return obs_raw, last_value, extras
 
     def update(self, last_value) -> Dict[str, float]:
-        if self.hip_update:      # one launch over the plan's own buffers (int64 dones), bit for bit compute_gae
+        if self._fused_update:      # one launch over the plan's own buffers (int64 dones), bit for bit compute_gae
             from ..policies.mlp_model import gae
             dones = self.rollout.dones if self.rollout is not None else self.b_done.long()
             ret, adv = gae(self.b_rew, self.b_val, dones, last_value, self.gamma, self.lam)
@@ -182,7 +198,7 @@ class PPO:
             kls = []
             for i in range(self.mb):
                 idx = slice(None) if perm is None else perm[i * n // self.mb:(i + 1) * n // self.mb]
-                if self.hip_update:
+                if self._fused_update:
                     # loss and gradient of the mini-batch in one fused launch (+ its reduction) straight into the flat .grad buffer; a permuted
                     # mini-batch is gathered with torch and handed over contiguous
                     self._hip_grad(*(t[idx] for t in (obs_n, act, old_logp, old_val_n, adv, ret_n)))
@@ -216,9 +232,16 @@ class PPO:
         return stats
 
     def _hip_grad(self, obs_n, act, old_logp, old_val_n, adv, ret_n):
-        """lm_mlp_ppo_grad on one mini-batch: fills the flat gradient buffer (the parameters' .grad views) and self._ppo_stats."""
-        from ..policies.mlp_model import mlp_ppo_grad, ppo_grad_workspace
+        """lm_mlp_ppo_grad / lm_gnn_ppo_grad on one mini-batch: fills the flat gradient buffer (the parameters' .grad views) and self._ppo_stats."""
         B = int(obs_n.shape[0])
+        if self.gnn_hip_update:
+            from ..policies.graph_model import gnn_ppo_grad, gnn_ppo_grad_workspace
+            if B not in self._ws:
+                self._ws[B] = gnn_ppo_grad_workspace(B, self.dev)
+            gnn_ppo_grad(self._flat, obs_n, act, old_logp, old_val_n, adv, ret_n, self.rclip, self.vclip, self.vscale, self.escale,
+                         grad=self._gflat, stats=self._ppo_stats, workspace=self._ws[B])
+            return
+        from ..policies.mlp_model import mlp_ppo_grad, ppo_grad_workspace
         if B not in self._ws:
             self._ws[B] = ppo_grad_workspace(self.n_obs, B, self.dev)
         mlp_ppo_grad(self._flat, obs_n, act, old_logp, old_val_n, adv, ret_n, self.rclip, self.vclip, self.vscale, self.escale,

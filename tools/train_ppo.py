@@ -22,7 +22,7 @@ def main():
     ap.add_argument("--no-obs-scaler", action="store_true", help="diagnostic: identity observation scaler")
     ap.add_argument("--no-hip", action="store_true", help="diagnostic: torch forward in the rollouts instead of the MFMA kernels")
     ap.add_argument("--no-fused", action="store_true", help="drive the rollout step by step from Python instead of the captured hipGraph")
-    ap.add_argument("--hip-update", action="store_true", help="MLP only: the update's loss gradient and GAE through the HIP kernels of csrc/lm_ppo.hip instead of autograd "
+    ap.add_argument("--hip-update", action="store_true", help="the update's loss gradient and GAE through the HIP kernels (csrc/lm_ppo.hip for --policy mlp, csrc/lm_gnn_ppo.hip for --policy gnn) instead of autograd "
                     "(off by default: DESIGN.md 5.4 has the measured comparison)")
     ap.add_argument("--max-lr", type=float, default=1e-2, help="diagnostic: cap of the KL-adaptive learning rate (skrl default 1e-2)")
     ap.add_argument("--min-log-std", type=float, default=None, help="diagnostic: floor of the log-std parameter (skrl clips at -20 only)")
@@ -53,7 +53,7 @@ def main():
         env.step = lambda act: _step(act[:, inv].contiguous())
         a.no_fused = True
     ppo = PPO(env, model, hip_inference=hip and not a.no_hip, fused_rollout=not a.no_fused, **({"kl_threshold": 0.0} if a.fixed_lr else {}), freeze_obs_scaler=a.no_obs_scaler, max_lr=a.max_lr, min_log_std=a.min_log_std,
-              hip_update=a.hip_update)
+              hip_update=a.hip_update and a.policy != "gnn", gnn_hip_update=a.hip_update and a.policy == "gnn")
     hist = ppo.train(a.timesteps, log_every=a.log_every, log=(lambda r: print(json.dumps(r), flush=True)) if rank == 0 else (lambda r: None))
     if rank == 0 and a.out:
         json.dump({"task": a.task, "num_envs": a.num_envs, "world": world, "policy": a.policy, "hip_update": bool(a.hip_update), "seed": a.seed, "history": hist}, open(a.out, "w"), indent=1)
