@@ -186,6 +186,50 @@ int lm_gnn_ppo_grad(const float* params, const float* obs_n, const float* action
 long long lm_gnn_ppo_grad_workspace(int B);
 int lm_gnn_ppo_grad_geometry(int B, int* tile, int* groups);
 
+/* ---- the optimiser step of the PPO update (csrc/lm_optim.hip): gradient-norm clip + Adam on one flat fp32 block (the blocks above, or any
+ * other), and the KL-adaptive learning rate, with the rate and the step count in device memory so that a caller's epoch loop never waits for
+ * the host.
+ *
+ * State block: device double [LM_OPTIM_STATE] (lm_optim_state_len() returns the length), 8-byte aligned.  Slots:
+ *   LM_OPTIM_LR the learning rate | LM_OPTIM_STEP Adam's step count | LM_OPTIM_GRAD_NORM, LM_OPTIM_CLIP_COEF of the last step |
+ *   LM_OPTIM_KL the mean the last lm_kl_adaptive_lr call took | 5, 6: lr / (1 - beta1^step) and sqrt(1 - beta2^step) of the last step
+ *   (derived by the step's first launch for its second) | 7 unused
+ * It is double so that the rate walks through the very doubles the host rule produces.  lm_optim_state_init sets lr and step, clip_coef = 1
+ * and the rest 0. */
+#define LM_OPTIM_STATE 8
+enum { LM_OPTIM_LR = 0, LM_OPTIM_STEP = 1, LM_OPTIM_GRAD_NORM = 2, LM_OPTIM_CLIP_COEF = 3, LM_OPTIM_KL = 4 };
+int lm_optim_state_len(void);
+int lm_optim_state_init(double* state, double lr, double step, void* stream);
+
+typedef struct lm_optim_hyper {
+  double beta1, beta2, eps;   /* Adam's (torch defaults 0.9, 0.999, 1e-8) */
+  double max_norm;            /* the gradient-norm clip */
+  int32_t clamp_offset;       /* entries [clamp_offset, clamp_offset + clamp_count) are floored at clamp_min after the step; */
+  int32_t clamp_count;        /*   clamp_count 0: no floor (clamp_offset is then not read) */
+  float clamp_min;
+  int32_t reserved0;          /* 0 */
+} lm_optim_hyper;
+
+/* One optimiser step on params [n]: torch.nn.utils.clip_grad_norm_(max_norm, error_if_nonfinite = False) followed by torch.optim.Adam
+ * (no weight decay, no amsgrad), with lr = state[LM_OPTIM_LR]:
+ *   norm = ||grad||_2 over all n;  coef = min(1, max_norm / (norm + 1e-6));  g = coef grad;  step += 1
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;  p -= (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ *   p[e] = max(p[e], clamp_min) for e in the clamp range
+ * evaluated per element in double and rounded once to fp32 per stored value (m, v, p); the squared norm is summed in double in an order fixed
+ * by n.  grad is read only (it is not scaled in place).  step, grad_norm and clip_coef are left in state.  Non-finite gradients propagate as
+ * they do in torch.  Two launches: one workgroup that writes state, then the step, which only reads it; no atomics; two calls on equal
+ * inputs write equal bits.
+ * params, grad, exp_avg, exp_avg_sq: device fp32 [n], 16-byte aligned (n itself is arbitrary: a scalar tail follows the 16-byte vectors).
+ * Returns 0; LM_EINVAL (-1) for a null pointer, n < 1, a clamp range outside [0, n), a misaligned block, or buffers that are not memory of the
+ * calling thread's current device - nothing is launched; -2 for a launch failure. */
+int lm_adam_clip_step(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int n, double* state, const lm_optim_hyper* hyper,
+                      void* stream);
+
+/* The KL-adaptive rate of train/ppo.py PPO.update (skrl KLAdaptiveRL): kl_mean = the mean of kl [count] (device fp32, summed in double in
+ * index order);  if threshold > 0:  kl_mean > 2 threshold: lr = max(lr / 1.5, lr_min);  else kl_mean < threshold / 2: lr = min(lr * 1.5, lr_max).
+ * Writes state[LM_OPTIM_LR] and state[LM_OPTIM_KL] = kl_mean.  Returns as above (count < 1 is LM_EINVAL). */
+int lm_kl_adaptive_lr(double* state, const float* kl, int count, double threshold, double lr_min, double lr_max, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,8 @@ EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy",
            "lm_rollout_set_deterministic", "lm_rollout_set_episode_record", "lm_episode_update",
            "lm_mlp_grad_param_count", "lm_mlp_ppo_grad", "lm_mlp_ppo_grad_workspace", "lm_mlp_ppo_grad_geometry", "lm_gae",
-           "lm_gnn_grad_param_count", "lm_gnn_ppo_grad", "lm_gnn_ppo_grad_workspace", "lm_gnn_ppo_grad_geometry"]
+           "lm_gnn_grad_param_count", "lm_gnn_ppo_grad", "lm_gnn_ppo_grad_workspace", "lm_gnn_ppo_grad_geometry",
+           "lm_optim_state_len", "lm_optim_state_init", "lm_adam_clip_step", "lm_kl_adaptive_lr"]
 
 # rows of the SoA float state
 ROW = dict(base_pos=0, base_quat=3, base_lin=7, base_ang=10, q=13, qd=25, plate_pos=37, plate_quat=40, plate_lin=44,
@@ -107,6 +108,12 @@ _DR_FAMILIES = (("dr_reset", make_reset_dr, "lm_set_reset_randomization"), ("dr_
 class LmPpoHyper(C.Structure):
     """lm_ppo_hyper (include/lm_policy.h): ratio clip, value clip, value-loss scale, entropy scale."""
     _fields_ = [("ratio_clip", C.c_float), ("value_clip", C.c_float), ("value_scale", C.c_float), ("entropy_scale", C.c_float)]
+
+
+class LmOptimHyper(C.Structure):
+    """lm_optim_hyper (include/lm_policy.h): Adam's betas and eps, the gradient-norm clip, the optional floor range."""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_norm", C.c_double),
+                ("clamp_offset", C.c_int32), ("clamp_count", C.c_int32), ("clamp_min", C.c_float), ("reserved0", C.c_int32)]
 
 
 ABI_VERSION = 5          # LM_ABI_VERSION of include/lm_engine.h this mirror was written against
@@ -201,7 +208,7 @@ def hipcc_command(extra, out):
     # LDS stores) needs no v_accvgpr_read per element (504 of them in k_gnn_forward)
     return [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
             "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"),
-            os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), os.path.join(_CSRC, "lm_gnn_ppo.hip"), "-o", out]
+            os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), os.path.join(_CSRC, "lm_gnn_ppo.hip"), os.path.join(_CSRC, "lm_optim.hip"), "-o", out]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -268,6 +275,9 @@ def load_library() -> C.CDLL:
     lib.lm_gnn_ppo_grad.argtypes = [fp, fp, fp, fp, fp, fp, fp, ip, C.POINTER(LmPpoHyper), fp, fp, vp, C.c_longlong, vp]
     lib.lm_gnn_ppo_grad_workspace.argtypes = [ip]; lib.lm_gnn_ppo_grad_workspace.restype = C.c_longlong
     lib.lm_gnn_ppo_grad_geometry.argtypes = [ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.lm_optim_state_init.argtypes = [fp, C.c_double, C.c_double, vp]
+    lib.lm_adam_clip_step.argtypes = [fp, fp, fp, fp, ip, fp, C.POINTER(LmOptimHyper), vp]
+    lib.lm_kl_adaptive_lr.argtypes = [fp, fp, ip, C.c_double, C.c_double, C.c_double, vp]
     lib.lm_last_error.restype = C.c_char_p
     lib.lm_version.restype = C.c_char_p
     _lib = lib

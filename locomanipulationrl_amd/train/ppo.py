@@ -8,7 +8,8 @@ skrl itself is third-party and not installed here; this trainer exists so that t
 exchange of SURVEY 8(e): rollout returns / advantages are all-gathered over RCCL for global advantage normalisation and
 the gradients are all-reduced.  Rollouts use the matrix-core policy forward (csrc/lm_policy.hip); updates use autograd, or - opt-in - the
 fused loss-gradient kernels and the GAE kernel: PPO(hip_update=True) for the SharedMLP (csrc/lm_ppo.hip),
-PPO(gnn_hip_update=True) for the GraphPolicy (csrc/lm_gnn_ppo.hip).
+PPO(gnn_hip_update=True) for the GraphPolicy (csrc/lm_gnn_ppo.hip).  With either of them, PPO(hip_optimizer=True) also runs the gradient-norm
+clip, Adam and the KL-adaptive rate on the device (csrc/lm_optim.hip): the epoch loop then holds no torch optimiser launch and no host wait.
 """
 from __future__ import annotations
 
@@ -82,9 +83,15 @@ def ppo_loss(model_outputs, act, old_logp, old_val_n, adv, ret_n, rclip, vclip, 
 class PPO:
     def __init__(self, env, model, rollouts=48, learning_epochs=5, mini_batches=1, gamma=0.99, lam=0.95, lr=3e-4, kl_threshold=0.012,
                  grad_norm_clip=1.0, ratio_clip=0.2, value_clip=0.2, value_loss_scale=1.0, entropy_loss_scale=0.0, hip_inference=True,
-                 fused_rollout=True, freeze_obs_scaler=False, max_lr=1e-2, min_log_std=None, hip_update=False, gnn_hip_update=False):
+                 fused_rollout=True, freeze_obs_scaler=False, max_lr=1e-2, min_log_std=None, hip_update=False, gnn_hip_update=False,
+                 hip_optimizer=False):
         self.env, self.model = env, model
         self.dev = next(model.parameters()).device
+        self.phase_marks = None       # timing hook: see _mark
+        self.hip_optimizer = bool(hip_optimizer)
+        if self.hip_optimizer and not (hip_update or gnn_hip_update):
+            raise ValueError("hip_optimizer=True steps the flat parameter blocks of a fused update: pass hip_update=True (SharedMLP) or gnn_hip_update=True "
+                             "(GraphPolicy) as well")
         self.hip_update = bool(hip_update)
         if self.hip_update:
             # no CPU fallback and no quiet autograd path, as in lib.Engine: say why and stop
@@ -118,6 +125,14 @@ class PPO:
         self.gamma, self.lam, self.lr, self.kl_thr = gamma, lam, lr, kl_threshold
         self.gclip, self.rclip, self.vclip, self.vscale, self.escale = grad_norm_clip, ratio_clip, value_clip, value_loss_scale, entropy_loss_scale
         self.opt = torch.optim.Adam(model.parameters(), lr=lr)
+        if self.hip_optimizer:
+            # Adam's moments as two flat blocks laid out like the parameters, the rate and the step count in a device state block; self.opt
+            # keeps the hyper-parameters and is the checkpoint format (filled from the blocks when saving, emptied into them when loading)
+            from ..policies.optim import optim_state
+            self._m, self._v = torch.zeros_like(self._flat), torch.zeros_like(self._flat)
+            self._ostate = optim_state(self.dev, lr, 0)
+            self._fetch = torch.zeros(self._ostate.numel() + 2, device=self.dev, dtype=torch.float64)
+            self._stats_all, self.last_kls = None, None
         self.freeze_obs_scaler = freeze_obs_scaler          # diagnostics: identity observation scaler (mean 0, var 1)
         self.max_lr, self.min_log_std = max_lr, min_log_std  # diagnostics: cap of the KL-adaptive rate (skrl: 1e-2); floor of log_std (skrl: -20)
         self.n_obs = int(env.observation_space.shape[0])          # 88 for the custom-controller tasks
@@ -175,13 +190,20 @@ class PPO:
         _, _, last_value = self._policy(obs_raw)
         return obs_raw, last_value, extras
 
+    def _mark(self, phase):
+        """Timing hook (tools/bench_ppo_update.py): with self.phase_marks a list, a device event is recorded at each phase boundary of update()."""
+        if self.phase_marks is not None:
+            ev = torch.cuda.Event(enable_timing=True); ev.record(); self.phase_marks.append((phase, ev))
+
     def update(self, last_value) -> Dict[str, float]:
+        self._mark("start")
         if self._fused_update:      # one launch over the plan's own buffers (int64 dones), bit for bit compute_gae
             from ..policies.mlp_model import gae
             dones = self.rollout.dones if self.rollout is not None else self.b_done.long()
             ret, adv = gae(self.b_rew, self.b_val, dones, last_value, self.gamma, self.lam)
         else:
             ret, adv = D.compute_gae(self.b_rew, self.b_val, self.b_done, last_value, self.gamma, self.lam)
+        self._mark("gae")
         g_ret, g_adv = D.all_gather_rollout(ret, adv)                 # RCCL all-gather over xGMI when world > 1
         adv = (adv - g_adv.mean()) / (g_adv.std() + 1e-8)             # global advantage normalisation
         obs, act = self.b_obs.reshape(-1, self.n_obs), self.b_act.reshape(-1, 12)
@@ -193,6 +215,15 @@ class PPO:
         n = obs.shape[0]; stats = {}
         # what the mini-batches below are cut from (references, no copies): read by the tests of the HIP update
         self.last_batch = {"obs_n": obs_n, "act": act, "old_logp": old_logp, "old_val_n": old_val_n, "adv": adv, "ret_n": ret_n, "ret": ret}
+        self._mark("normalise")
+        if self.hip_optimizer:
+            from ..policies.optim import STATE
+            self._run_epochs(obs_n, act, old_logp, old_val_n, adv, ret_n)
+            self._mark("epochs")
+            h = self._fetch.cpu()                                                  # the update's one device-to-host copy
+            self.lr = float(h[STATE["lr"]])
+            for gp in self.opt.param_groups: gp["lr"] = self.lr
+            return {"kl": float(h[STATE["kl"]]), "loss_pi": float(h[-2]), "loss_v": float(h[-1]), "lr": self.lr}
         for epoch in range(self.epochs):
             perm = torch.randperm(n, device=self.dev) if self.mb > 1 else None
             kls = []
@@ -229,28 +260,93 @@ class PPO:
                 elif kl < self.kl_thr / 2: self.lr = min(self.lr * 1.5, self.max_lr)
             for gp in self.opt.param_groups: gp["lr"] = self.lr
             stats = {"kl": kl, "loss_pi": float(loss_pi), "loss_v": float(loss_v), "lr": self.lr}
+        self._mark("epochs")
         return stats
 
-    def _hip_grad(self, obs_n, act, old_logp, old_val_n, adv, ret_n):
-        """lm_mlp_ppo_grad / lm_gnn_ppo_grad on one mini-batch: fills the flat gradient buffer (the parameters' .grad views) and self._ppo_stats."""
-        B = int(obs_n.shape[0])
+    def _run_epochs(self, obs_n, act, old_logp, old_val_n, adv, ret_n):
+        """The epoch loop of hip_optimizer=True: per mini-batch the fused gradient launch and lm_adam_clip_step, per epoch lm_kl_adaptive_lr on
+        that epoch's KL values.  Nothing in here waits for the device: the statistics of every mini-batch stay in self._stats_all, the KL
+        values of epoch e in self.last_kls[e], and the state block plus the last loss_pi / loss_v are left in self._fetch for update()'s
+        one copy to the host."""
+        from ..policies.optim import adam_clip_step, kl_adaptive_lr
+        n, E, mb = obs_n.shape[0], self.epochs, self.mb
+        if self._stats_all is None or self._stats_all.shape[0] != E * mb:
+            self._stats_all = torch.zeros(E * mb, 4, device=self.dev)
+            self.last_kls = self._stats_all[:, 2].unflatten(0, (E, mb))               # a view: (epoch, mini-batch)
+        b1, b2 = self.opt.defaults["betas"]; eps = self.opt.defaults["eps"]
+        clamp = None if self.min_log_std is None else (self._offsets["log_std_parameter"][0], 12, self.min_log_std)
+        for epoch in range(E):
+            perm = torch.randperm(n, device=self.dev) if mb > 1 else None
+            for i in range(mb):
+                idx = slice(None) if perm is None else perm[i * n // mb:(i + 1) * n // mb]
+                self._hip_grad(*(t[idx] for t in (obs_n, act, old_logp, old_val_n, adv, ret_n)), stats=self._stats_all[epoch * mb + i])
+                if self.world > 1:
+                    dist.all_reduce(self._gflat); self._gflat /= self.world
+                adam_clip_step(self._flat, self._gflat, self._m, self._v, self._ostate, b1, b2, eps, self.gclip, clamp)
+            kls = self.last_kls[epoch]
+            if mb > 1 or self.world > 1:
+                kls = kls.contiguous()                                                 # one value is its own contiguous row
+                if self.world > 1:
+                    dist.all_reduce(kls); kls /= self.world
+                    self.last_kls[epoch].copy_(kls)
+            kl_adaptive_lr(self._ostate, kls, self.kl_thr, 1e-6, self.max_lr)
+        ns = self._ostate.numel()
+        self._fetch[:ns].copy_(self._ostate); self._fetch[ns:].copy_(self._stats_all[-1, :2])
+
+    def _hip_grad(self, obs_n, act, old_logp, old_val_n, adv, ret_n, stats=None):
+        """lm_mlp_ppo_grad / lm_gnn_ppo_grad on one mini-batch: fills the flat gradient buffer (the parameters' .grad views) and `stats`
+        (self._ppo_stats when not given)."""
+        B = int(obs_n.shape[0]); stats = self._ppo_stats if stats is None else stats
         if self.gnn_hip_update:
             from ..policies.graph_model import gnn_ppo_grad, gnn_ppo_grad_workspace
             if B not in self._ws:
                 self._ws[B] = gnn_ppo_grad_workspace(B, self.dev)
             gnn_ppo_grad(self._flat, obs_n, act, old_logp, old_val_n, adv, ret_n, self.rclip, self.vclip, self.vscale, self.escale,
-                         grad=self._gflat, stats=self._ppo_stats, workspace=self._ws[B])
+                         grad=self._gflat, stats=stats, workspace=self._ws[B])
             return
         from ..policies.mlp_model import mlp_ppo_grad, ppo_grad_workspace
         if B not in self._ws:
             self._ws[B] = ppo_grad_workspace(self.n_obs, B, self.dev)
         mlp_ppo_grad(self._flat, obs_n, act, old_logp, old_val_n, adv, ret_n, self.rclip, self.vclip, self.vscale, self.escale,
-                     grad=self._gflat, stats=self._ppo_stats, workspace=self._ws[B])
+                     grad=self._gflat, stats=stats, workspace=self._ws[B])
 
     # ------------------------------------------------------------------ checkpoints (what the reference's agents write as best_agent.pt: policy,
     # value head, optimiser and both preprocessors; tools/eval_policy.py and train/evaluate.py read them back)
+    def _moments_to_opt(self):
+        """hip_optimizer: self.opt's state as torch.optim.Adam would hold it after the steps taken so far (copies of the flat blocks)."""
+        from ..policies.optim import STATE
+        step = float(self._ostate[STATE["step"]])
+        self.opt.state.clear()
+        if step > 0:
+            for name, p in self.model.named_parameters():
+                o, shape = self._offsets[name]
+                self.opt.state[p] = {"step": torch.tensor(step, dtype=torch.float32), "exp_avg": self._m[o:o + p.numel()].view(shape).clone(),
+                                     "exp_avg_sq": self._v[o:o + p.numel()].view(shape).clone()}
+
+    def _moments_from_opt(self):
+        """hip_optimizer: the flat blocks and the state block from what self.opt has just loaded (a parameter without state: zeros)."""
+        from ..policies.optim import optim_state
+        self._m.zero_(); self._v.zero_(); step = 0.0
+        for name, p in self.model.named_parameters():
+            st = self.opt.state.get(p)
+            if st:
+                o, _ = self._offsets[name]
+                self._m[o:o + p.numel()].copy_(st["exp_avg"].reshape(-1)); self._v[o:o + p.numel()].copy_(st["exp_avg_sq"].reshape(-1))
+                step = float(st["step"])
+        optim_state(self.dev, self.lr, step, state=self._ostate)
+        self.opt.state.clear()
+
     def state_dict(self):
-        return {"model": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}, "model_class": type(self.model).__name__,
+        if self.hip_optimizer:      # the checkpoint is torch.optim.Adam's in every mode
+            self._moments_to_opt()
+            try:
+                return self._state_dict()
+            finally:
+                self.opt.state.clear()
+        return self._state_dict()
+
+    def _state_dict(self):
+        return {"model":{k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}, "model_class": type(self.model).__name__,
                 "num_observations": self.n_obs, "obs_scaler": self.obs_scaler.state_dict(), "val_scaler": self.val_scaler.state_dict(),
                 "lr": float(self.lr), "optimizer": self.opt.state_dict()}
 
@@ -261,6 +357,8 @@ class PPO:
         self.opt.load_state_dict(sd["optimizer"])
         self.lr = float(sd["lr"])
         for gp in self.opt.param_groups: gp["lr"] = self.lr
+        if self.hip_optimizer:
+            self._moments_from_opt()
 
     def save(self, path):
         torch.save(self.state_dict(), path)

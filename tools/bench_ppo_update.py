@@ -2,10 +2,15 @@
 """Time the PPO update of the reference recipe (T 48, N 4096, num_obs 64, 5 epochs, 1 mini-batch) in both modes, on buffers of one real
 fused rollout: the torch update() against the HIP update() (PPO(hip_update=True): lm_mlp_ppo_grad + lm_gae), and compute_gae against lm_gae.
 
-    python tools/bench_ppo_update.py [--policy mlp|gnn] [--reps 20] [--warmup 3] [--out profiles/ppo_update_bench.json]
+    python tools/bench_ppo_update.py [--policy mlp|gnn] [--hip-optimizer] [--reps 20] [--warmup 3] [--out profiles/ppo_update_bench.json]
 
 --policy gnn times the GraphPolicy's update the same way (PPO(gnn_hip_update=True): lm_gnn_ppo_grad + lm_gae, on QuadrupedPoseControlVertical) and
-writes profiles/gnn_update_bench.json; the default, mlp, is unchanged.
+writes profiles/gnn_update_bench.json; the default, mlp, is unchanged.  --hip-optimizer adds a third alternated path, the HIP update with the
+optimiser step on the device as well (PPO(hip_optimizer=True): lm_adam_clip_step + lm_kl_adaptive_lr), and writes
+profiles/ppo_update_bench_optimizer.json (gnn: profiles/gnn_update_bench_optimizer.json).
+
+Every path is also split into phases by device events at update()'s phase boundaries (PPO.phase_marks): GAE | all-gather, advantage
+normalisation, both scalers and the normalisation of the batch | the epoch loop.  The events are recorded inside the timed call (four records).
 
 Protocol: one process, two trainers on two engines with the same seed (identical rollouts), each warmed up; the two paths are timed
 alternately (torch, hip, torch, hip, ...) with a device event on either side of each call, so clock and thermal drift hit both alike.  Every
@@ -39,32 +44,39 @@ def main():
     ap.add_argument("--num-envs", type=int, default=4096); ap.add_argument("--rollouts", type=int, default=48); ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20); ap.add_argument("--warmup", type=int, default=3); ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--policy", choices=("mlp", "gnn"), default="mlp")
+    ap.add_argument("--hip-optimizer", action="store_true", help="a third alternated path: the HIP update with clip + Adam + the KL-adaptive rate on the device")
     ap.add_argument("--out", default=None, help="default: profiles/ppo_update_bench.json (mlp), profiles/gnn_update_bench.json (gnn)")
     a = ap.parse_args()
     assert a.reps >= 2
     gnn = a.policy == "gnn"
     if a.out is None:
-        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gnn_update_bench.json" if gnn else "ppo_update_bench.json")
+        a.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", ("gnn_update_bench" if gnn else "ppo_update_bench") + ("_optimizer" if a.hip_optimizer else "") + ".json")
+    modes = ("torch", "hip", "hip_optimizer") if a.hip_optimizer else ("torch", "hip")
     tr = {}
-    for mode in ("torch", "hip"):
+    for mode in modes:
         torch.manual_seed(a.seed)
         env = lm.make_env("QuadrupedPoseControlVertical" if gnn else "QuadrupedPoseControl", num_envs=a.num_envs, seed=a.seed)
         if gnn:
             from locomanipulationrl_amd.policies.graph_model import GraphPolicy
-            ppo = PPO(env, GraphPolicy().to("cuda:0"), rollouts=a.rollouts, learning_epochs=a.epochs, gnn_hip_update=(mode == "hip"))
+            ppo = PPO(env, GraphPolicy().to("cuda:0"), rollouts=a.rollouts, learning_epochs=a.epochs, gnn_hip_update=(mode != "torch"), hip_optimizer=(mode == "hip_optimizer"))
         else:
-            ppo = PPO(env, SharedMLP(64).to("cuda:0"), rollouts=a.rollouts, learning_epochs=a.epochs, hip_update=(mode == "hip"))
+            ppo = PPO(env, SharedMLP(64).to("cuda:0"), rollouts=a.rollouts, learning_epochs=a.epochs, hip_update=(mode != "torch"), hip_optimizer=(mode == "hip_optimizer"))
         obs = env.reset()["obs"]
         obs, last_value, _ = ppo.collect(obs)                    # one real fused rollout fills the buffers both updates read
         tr[mode] = (env, ppo, last_value.clone(), ppo.state_dict())
-    times = {"torch": [], "hip": []}
+    times = {m: [] for m in modes}
+    phases = {m: {"gae": [], "normalise": [], "epochs": []} for m in modes}
     for rep in range(a.warmup + a.reps):
-        for mode in ("torch", "hip"):
+        for mode in modes:
             _, ppo, last_value, sd = tr[mode]
             ppo.load_state_dict(sd)
+            ppo.phase_marks = []
             ms = timed(lambda: ppo.update(last_value))
+            marks, ppo.phase_marks = ppo.phase_marks, None
             if rep >= a.warmup:
                 times[mode].append(ms)
+                for (_, e0), (name, e1) in zip(marks, marks[1:]):
+                    phases[mode][name].append(e0.elapsed_time(e1))
     _, ppo, last_value, _ = tr["hip"]
     rew, val, dones = ppo.b_rew, ppo.b_val, ppo.rollout.dones
     dones_f = dones.float()
@@ -86,17 +98,27 @@ def main():
                 "flop_note": "2 x (forward + delta + dW) x weights x samples, minus the delta product of layer 1 (no gradient flows into the observations)"}
     res = {"shape": {"T": a.rollouts, "N": a.num_envs, "B": B, "num_obs": 64, "epochs": a.epochs, "mini_batches": 1},
            "protocol": "one process, alternating torch / hip, device events around each call, state restored before each, warmup %d" % a.warmup,
-           "update": {k: summary(v) for k, v in times.items()}, "gae": {k: summary(v) for k, v in gt.items()},
+           "update": {k: summary(v) for k, v in times.items()},
+           "phases": {m: {k: summary(v) for k, v in ph.items()} for m, ph in phases.items()},
+           "phases_note": "device events at update()'s phase boundaries, inside the timed call: gae | all-gather, advantage normalisation, scalers, batch normalisation | "
+                          "epoch loop (torch / hip: its float(kl) waits included; hip_optimizer: up to the one copy to the host, which is not in any phase)",
+           "gae": {k: summary(v) for k, v in gt.items()},
            "kernel": kern,
            "device": torch.cuda.get_device_name(0)}
     u = res["update"]
-    spread = max(abs(u[m]["median_first_half_ms"] - u[m]["median_second_half_ms"]) for m in u)
+    spread = max(abs(u[m]["median_first_half_ms"] - u[m]["median_second_half_ms"]) for m in ("torch", "hip"))
     res["update_speedup_median"] = u["torch"]["median_ms"] / u["hip"]["median_ms"]
     res["update_run_to_run_spread_ms"] = spread
     res["hip_beats_torch_beyond_spread"] = bool(u["torch"]["median_ms"] - u["hip"]["median_ms"] > spread)
     if gnn:
         res["policy"] = "gnn"
         res["hip_p25_p75_entirely_below_torch"] = bool(u["hip"]["p75_ms"] < u["torch"]["p25_ms"])
+    if a.hip_optimizer:
+        res["policy"] = a.policy
+        res["hip_optimizer_minus_hip_median_ms"] = u["hip_optimizer"]["median_ms"] - u["hip"]["median_ms"]
+        res["hip_optimizer_drift_ms"] = abs(u["hip_optimizer"]["median_first_half_ms"] - u["hip_optimizer"]["median_second_half_ms"])
+        res["hip_optimizer_p25_p75_entirely_below_hip"] = bool(u["hip_optimizer"]["p75_ms"] < u["hip"]["p25_ms"])      # the rule: an improvement only if the quartile ranges are disjoint
+        res["protocol"] = res["protocol"].replace("alternating torch / hip", "alternating torch / hip / hip_optimizer")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1)
     print(json.dumps(res))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Behavioural acceptance run: train the reference's PPO recipe on the engine and log the success-rate curve.
-    python tools/train_ppo.py --task QuadrupedPoseControl --num-envs 4096 --timesteps 4800 [--policy mlp|gnn] [--hip-update] [--out profiles/x.json] [--save agent.pt]
+    python tools/train_ppo.py --task QuadrupedPoseControl --num-envs 4096 --timesteps 4800 [--policy mlp|gnn] [--hip-update [--hip-optimizer]] [--out profiles/x.json] [--save agent.pt]
 (multi-GPU: python -m torch.distributed.run --nproc-per-node N tools/train_ppo.py ...)"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,10 +24,14 @@ def main():
     ap.add_argument("--no-fused", action="store_true", help="drive the rollout step by step from Python instead of the captured hipGraph")
     ap.add_argument("--hip-update", action="store_true", help="the update's loss gradient and GAE through the HIP kernels (csrc/lm_ppo.hip for --policy mlp, csrc/lm_gnn_ppo.hip for --policy gnn) instead of autograd "
                     "(off by default: DESIGN.md 5.4 has the measured comparison)")
+    ap.add_argument("--hip-optimizer", action="store_true", help="with --hip-update: the gradient-norm clip, Adam and the KL-adaptive rate on the device too (csrc/lm_optim.hip); "
+                    "the epoch loop then never waits for the host (DESIGN.md 5.4)")
     ap.add_argument("--max-lr", type=float, default=1e-2, help="diagnostic: cap of the KL-adaptive learning rate (skrl default 1e-2)")
     ap.add_argument("--min-log-std", type=float, default=None, help="diagnostic: floor of the log-std parameter (skrl clips at -20 only)")
     ap.add_argument("--engine", action="append", default=[], metavar="KEY=VALUE", help="diagnostic: a sim.engine override of the task YAML, e.g. friction_scale=1.0")
     a = ap.parse_args()
+    if a.hip_optimizer and not a.hip_update:
+        ap.error("--hip-optimizer steps the flat parameter blocks of the fused update: it needs --hip-update")
     # LM_DIST_BACKEND=gloo: rehearsal of the multi-rank path on a box with fewer GPUs than ranks (ranks then share devices)
     backend = os.environ.get("LM_DIST_BACKEND")
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -53,10 +57,10 @@ def main():
         env.step = lambda act: _step(act[:, inv].contiguous())
         a.no_fused = True
     ppo = PPO(env, model, hip_inference=hip and not a.no_hip, fused_rollout=not a.no_fused, **({"kl_threshold": 0.0} if a.fixed_lr else {}), freeze_obs_scaler=a.no_obs_scaler, max_lr=a.max_lr, min_log_std=a.min_log_std,
-              hip_update=a.hip_update and a.policy != "gnn", gnn_hip_update=a.hip_update and a.policy == "gnn")
+              hip_update=a.hip_update and a.policy != "gnn", gnn_hip_update=a.hip_update and a.policy == "gnn", hip_optimizer=a.hip_optimizer)
     hist = ppo.train(a.timesteps, log_every=a.log_every, log=(lambda r: print(json.dumps(r), flush=True)) if rank == 0 else (lambda r: None))
     if rank == 0 and a.out:
-        json.dump({"task": a.task, "num_envs": a.num_envs, "world": world, "policy": a.policy, "hip_update": bool(a.hip_update), "seed": a.seed, "history": hist}, open(a.out, "w"), indent=1)
+        json.dump({"task": a.task, "num_envs": a.num_envs, "world": world, "policy": a.policy, "hip_update": bool(a.hip_update), "hip_optimizer": bool(a.hip_optimizer), "seed": a.seed, "history": hist}, open(a.out, "w"), indent=1)
     if rank == 0 and a.save:
         ppo.save(a.save)
     env.close()
