@@ -306,7 +306,9 @@ int lm_enable_contact_forces(lm_engine* h, int on);
  * and adds the observation noise (obs_buf and out_obs); the staged entry points below refuse a randomised engine.
  * One kernel launch.  Un-randomised velocity-drive locomotion engines of more than 32 768 envs get the build of the same kernel for two
  * wavefronts per SIMD (k_step_w2: same bits, faster beyond two generations of workgroups; the environment variable LM_W2_MIN_ENVS, read
- * by lm_create, moves that threshold). */
+ * by lm_create, moves that threshold).  Un-randomised velocity-drive engines with a locomotion block, small enough that two wavefronts per
+ * 16 envs still find a SIMD each (8192 envs on MI355X), get the kernel with a helper wavefront per workgroup (k_step_h2: same bits; the
+ * environment variable LM_H2_MAX_ENVS, read by lm_create, moves that threshold, 0 = never). */
 int lm_step(lm_engine* h, const float* actions, const float* goal_rand, float* out_obs, float* out_states,
             float* out_rew, int64_t* out_resets, float* out_extras, void* stream);
 

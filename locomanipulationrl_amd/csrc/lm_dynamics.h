@@ -160,12 +160,16 @@ LM_DEV SV sel(bool c, SV a, SV b) { return sv(sel(c, a.w, b.w), sel(c, a.v, b.v)
 
 // MASS = 1 (the randomised kernels with the body-mass channel on): the masses of the five bodies come from the caller instead of the table;
 // COM and inertia about the COM stay the table's
-template <int MASS = 0>
+// PART (k_step_h2, lm_engine_h2.hip): 0 = both chains below; 1 = the inertia chain only (wavefront 0: fcs and hq are left unset and come from the
+// helper wavefront through LDS); 2 = the bias chain only (the helper: only fcs and hq are set).  After the placed inertias the chains share no
+// value, and each is compiled from the lines every other kernel compiles
+template <int MASS = 0, int PART = 0>
 LM_DEV void limb_dynamics(const float* tl, const LimbKin& K, const float qd[3], SV v0, SV avp0, LimbDyn& D, float m_s = 0.f, f2 m_41 = f2{0.f, 0.f}, f2 m_32 = f2{0.f, 0.f}) {
   const f2* tp = reinterpret_cast<const f2*>(tl);
   const SI Is = MASS ? place_inertia_m<float>(tl + T_I0, m_s, K.Rs, K.os) : place_inertia<float>(tl + T_I0, K.Rs, K.os);
   const SIP I41 = MASS ? place_inertia_m<f2>(tp + T_Q1 / 2, m_41, K.R41, K.o41) : place_inertia<f2>(tp + T_Q1 / 2, K.R41, K.o41),
             I32 = MASS ? place_inertia_m<f2>(tp + T_Q2 / 2, m_32, K.R32, K.o32) : place_inertia<f2>(tp + T_Q2 / 2, K.R32, K.o32);
+  if (PART != 1) {
   // velocities / velocity-product accelerations down the two chains
   const SV j1 = qd[0] * K.s1; const SVP j23 = mk2(qd[1], qd[2]) * K.s23, jp = mk2(K.pd, -K.pd) * K.sp12;
   const SV vs = v0 + j1; const SVP v41 = bc(vs) + j23, v32 = v41 + jp;
@@ -180,6 +184,9 @@ LM_DEV void limb_dynamics(const float* tl, const LimbKin& K, const float qd[3], 
   const float h1 = sdot(K.s1, D.fcs); const f2 h23 = sdot(K.s23, fc), hp = sdot(K.sp12, p32);      // (h2 | h3), (hp1 | hp2)
   const float g1 = K.g1, dh = hp.x - hp.y;
   D.hq[0] = h1; D.hq[1] = h23.x + g1 * dh; D.hq[2] = h23.y - g1 * dh;
+  }
+  if (PART == 2) return;
+  const float g1 = K.g1;
   // composite inertias and the columns of the coupling / joint-space inertia
   const SIP Ic = I41 + I32;                                             // (I4c | I1c)
   D.Isc = Is + lo(Ic) + hi(Ic);
@@ -385,6 +392,13 @@ LM_DEV void integrate_free(FreeBody& F, const M3& R, float dt) {
 // (-DLM_WAVES2 on the whole library, tools/ab_build.py, is the A/B build of round 4: every step kernel then has this layout.)
 #define STASH_SLOTS 18
 #define LM_STEP_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
+#elif defined(LM_HELPER_WAVE)
+// k_step_h2 (lm_engine_h2.hip): a second wavefront of the workgroup computes the limb bias terms (see helper_wave below).  The two wavefronts
+// exchange 16 + 9 floats per lane and sub-step through seven more slots of the same [slot][lane] array
+#define STASH_SLOTS 29
+#define HAND_IN 22            // 4 slots, wavefront 0 -> helper: q, qd | qd, u.w | u.w, u.v | row 2 of the base's rotation
+#define HAND_OUT 26           // 3 slots, helper -> wavefront 0: fcs | fcs, hq | hq
+#define LM_STEP_ATTR
 #else
 #define STASH_SLOTS 22
 #define LM_STEP_ATTR
@@ -394,6 +408,19 @@ struct Stash {
   LM_DEV void put(int slot, float a, float b, float c, float d) const { base[slot * 64 + lane] = make_float4(a, b, c, d); }
   LM_DEV float4 get(int slot) const { return base[slot * 64 + lane]; }
 };
+#ifdef LM_HELPER_WAVE
+// Workgroup barrier of k_step_h2 for data exchanged through LDS: waits for this wavefront's LDS operations only (not for loads and stores in
+// flight), and keeps the scheduler from moving arithmetic across it - wavefront 0 is to do all the work that does not need the helper's
+// result BEFORE it waits for that result.
+LM_DEV void hw_barrier() {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0)
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+#endif
 LM_DEV void stash_sv3(const Stash& S, int slot, SV a, SV b, SV c, float e0 = 0.f, float e1 = 0.f) {      // 18 floats -> 5 slots (the last one half used: e0, e1 ride there)
   S.put(slot + 0, a.w.x, a.w.y, a.w.z, a.v.x); S.put(slot + 1, a.v.y, a.v.z, b.w.x, b.w.y);
   S.put(slot + 2, b.w.z, b.v.x, b.v.y, b.v.z); S.put(slot + 3, c.w.x, c.w.y, c.w.z, c.v.x); S.put(slot + 4, c.v.y, c.v.z, e0, e1);
@@ -518,16 +545,20 @@ LM_DEV SI plate_inertia_env(const lm_params* __restrict__ P, float m, float s) {
 // One drive pass of a sub-step: the limb's joints eliminated against the given drive state (sat / tsat), the hub or plate solve, the contact
 // operator and the PGS, on the pass-invariant terms I - the registers substep() has just computed (first pass) or the stash's copy (second pass).
 // Out: the joint rates qdn and the free body's velocity un after the pass, and (CF) the contact impulses lamc.
-template <int MODE, int VAR, int DR, int CF>
+// HW 1 (the first pass of wavefront 0 of k_step_h2): I.hq and the bias halves PB[i].p.x are not in I; the pass fetches them from the helper
+// wavefront's slots (Hd) behind its second barrier, which stands where they are first needed - after the articulated hub inertia, so that
+// wavefront 0 has more work before the barrier than the helper has and does not wait there.
+template <int MODE, int VAR, int DR, int CF, int HW = 0>
 LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBody& F, const PassTerms& I, float dt, float kd, const float cjv[3],
                          const bool sat[3], const float tsat[3], const float tgt[3], const float qd[3], float bn, float mu_dr,
-                         bool mp_on, float m_plate, float s_plate, float qdn[3], SV& un, float lamc[3]) {
+                         bool mp_on, float m_plate, float s_plate, float qdn[3], SV& un, float lamc[3], const Stash* Hd = nullptr) {
   const S6 Fq0 = I.Fq0, Fq1 = I.Fq1, Fq2 = I.Fq2;
   float Ha[6] = {I.Ha[0], I.Ha[1], I.Ha[2], I.Ha[3], I.Ha[4], I.Ha[5]}, r[3];
   const float hq[3] = {I.hq[0], I.hq[1], I.hq[2]};
+  R4 PBh[6];      // HW: the rows with the helper's bias wrench
   const float Jq[3][3] = {{I.Jq0[0], I.Jq0[1], I.Jq0[2]}, {I.j12[0].x, I.j12[1].x, I.j12[2].x}, {I.j12[0].y, I.j12[1].y, I.j12[2].y}};
   const f2 j12[3] = {I.j12[0], I.j12[1], I.j12[2]};      // (Jq[1][c] | Jq[2][c])
-  const R4* PB = I.PB;
+  const R4* PB = HW ? PBh : I.PB;
   const int di[3] = {0, 3, 5};
 #pragma unroll
   for (int a = 0; a < 3; a++) {
@@ -542,7 +573,7 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
       Ha[di[a]] = fmaf(dt, sat[a] ? cj : kd + cj, Ha[di[a]]);                  // viscous joint damping is implicit in both cases
       const float rr = sat[a] ? tsat[a] : kd * (tgt[a] - qd[a]);
       const float damp = cj * qd[a];
-      r[a] = (rr - damp) - hq[a];
+      r[a] = HW ? rr - damp : (rr - damp) - hq[a];      // (HW: the joint-space bias is subtracted behind the barrier)
     }
   }
   float Hi[6]; inv3sym(Ha, Hi);
@@ -565,6 +596,20 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
         A[I][2 * jp + 1] = quad_sum(v.y); } }
     LM_AROW(0) LM_AROW(1) LM_AROW(2) LM_AROW(3) LM_AROW(4) LM_AROW(5)
 #undef LM_AROW
+#ifdef LM_HELPER_WAVE
+    if (HW) {
+      hw_barrier();      // the helper's second barrier of the sub-step: its bias terms are in LDS
+      const float4 b0 = Hd->get(HAND_OUT), b1 = Hd->get(HAND_OUT + 1), b2 = Hd->get(HAND_OUT + 2);
+      const float fcs[6] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y}, hqh[3] = {b1.z, b1.w, b2.x};
+#pragma unroll
+      for (int i = 0; i < 6; i++) { PBh[i].p = mk2(fcs[i], I.PB[i].p.y); PBh[i].q = I.PB[i].q; }
+#pragma unroll
+      for (int a = 0; a < 3; a++) {
+#pragma clang fp contract(off)
+        r[a] = r[a] - hqh[a];
+      }
+    }
+#endif
     Chol6 Ch; chol6(A, Ch);
     // (bias | row 0) and (row 1 | row 2) with the limb's joints eliminated:  P = PB + coefficient x K,  T_r = Jb_r - K Jq_r^T
     const f2 cp[3] = {mk2(r[0], -Jq[0][0]), mk2(r[1], -Jq[0][1]), mk2(r[2], -Jq[0][2])};
@@ -651,11 +696,59 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
   LM_STAMP(4);
 }
 
+#ifdef LM_HELPER_WAVE
+// The helper wavefront of k_step_h2 (threads 64-127; lane l serves lane l of wavefront 0).  Per locomotion sub-step it recomputes the limb
+// kinematics and the placed inertias from the joint state wavefront 0 published, runs the bias chain of limb_dynamics and the hub's own bias
+// term (limb 0 carries the hub, as in substep) and leaves the limb's bias wrench and joint-space bias for wavefront 0: about 900 instructions
+// that wavefront 0, which is bound by its own instruction stream, no longer issues.  It reads the table in LDS and the parameter block, and
+// touches no other memory.
+//
+// Same bits as k_step: the helper's inputs are values that k_step, too, holds rounded in registers at the top of a sub-step (loop-carried
+// state, or products that only feed further products), its outputs are values that k_step pins before the pass reads them (pin_terms), and
+// in between both kernels compile the same lines.  No expression straddles the cut in a way the compiler could contract differently: the only
+// sums of two products that meet across it are the components of Ic.h = I41.h + I32.h, where the product with fewer uses is fused, and that is
+// I41.h with and without the bias chain (I32 also feeds Fp).  The fictitious acceleration is handed over as row 2 of the base's rotation, not
+// as gravity x that row, because k_step fuses that product into the shell's acceleration.
+//
+// Barriers: two per sub-step in each wavefront, in straight-line code outside every branch of the sub-step (second pass, reset, lane
+// divergence); both wavefronts take nsub from the same kernel argument or the same word of the parameter block, so they arrive the same number
+// of times.  Inactive lanes of a ragged wavefront run along.  No flag in memory is polled anywhere.  A wavefront that has ended no longer counts
+// at a barrier, so a helper that returns at once (manipulation block, nsub = 0) cannot hold wavefront 0 up, and a mismatch could not hang: it
+// would show as wrong bits (tests/test_gpu_helper_wave.py).
+// Hazards: the helper reads HAND_IN between the barriers and wavefront 0 writes it before the first; wavefront 0 reads HAND_OUT after the second
+// and has its data (lgkmcnt(0)) before the next sub-step's first barrier, behind which the helper writes it again.
+LM_DEV void helper_wave(const lm_params* __restrict__ P, const float* sTab, float4* sStash, int lane, int nsub) {
+  const int limb = lane & 3;
+  const float* th = sTab; const float* tl = sTab + HUB_FLOATS + limb * LIMB_STRIDE;
+  Stash St; St.base = sStash; St.lane = lane;
+  const float gravity = P->gravity;
+  for (int s = 0; s < nsub; s++) {
+    hw_barrier();      // the joint state of this sub-step is published (first sub-step: and the table committed)
+    const float4 h0 = St.get(HAND_IN), h1 = St.get(HAND_IN + 1), h2 = St.get(HAND_IN + 2), h3 = St.get(HAND_IN + 3);
+    const float q[3] = {h0.x, h0.y, h0.z}, qd[3] = {h0.w, h1.x, h1.y};
+    const SV v0 = sv(v3(h1.z, h1.w, h2.x), v3(h2.y, h2.z, h2.w));
+    const SV avp0 = sv(v3(0, 0, 0), gravity * v3(h3.x, h3.y, h3.z));      // fictitious acceleration = -gravity
+    LimbKin K; limb_kinematics(tl, q, qd, K);
+    LimbDyn D; limb_dynamics<0, 2>(tl, K, qd, v0, avp0, D);
+    {
+      // the hub's own bias term, as in substep()
+      const float m0 = (limb == 0) ? 1.f : 0.f;
+      SI I0 = hub_inertia(th);
+      I0.m *= m0; I0.h = m0 * I0.h; I0.xx *= m0; I0.yy *= m0; I0.zz *= m0; I0.xy *= m0; I0.xz *= m0; I0.yz *= m0;
+      D.fcs = D.fcs + I0 * avp0 + fcross(v0, I0 * v0);
+    }
+    St.put(HAND_OUT, D.fcs.w.x, D.fcs.w.y, D.fcs.w.z, D.fcs.v.x); St.put(HAND_OUT + 1, D.fcs.v.y, D.fcs.v.z, D.hq[0], D.hq[1]); St.put(HAND_OUT + 2, D.hq[2], 0.f, 0.f, 0.f);
+    hw_barrier();      // the bias terms are in LDS
+  }
+}
+#endif
+
 // One physics sub-step of one env (4 lanes).  MODE 0: F is the robot base.  MODE 1: F is the plate, the
 // robot base is fixed at (Rb, pb).
 // CF 1 (the contact-force reporting kernels): cf[0..2] += the world-frame contact impulse on this lane's foot, cf[3] += 1 when
 // the foot is loaded (lam_n > 0), both from the impulses of the sub-step's last pass.
-template <int MODE, int VAR, int DR, int CF = 0, int REG0 = 1>
+// HW 1 (wavefront 0 of k_step_h2; locomotion, no DR, first pass on registers): the limb's bias terms come from the helper wavefront (helper_wave).
+template <int MODE, int VAR, int DR, int CF = 0, int REG0 = 1, int HW = 0>
 LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const float* tl, int limb, const Stash& St,
                     FreeBody& F, const M3& Rfix, V3 pfix, float q[3], float qd[3], const float tgt[3], float tau_acc[3], const DrPhys& X, float* cf = nullptr) {
   const float dt = P->dt, kd = DR ? X.kd : P->kd;      // DR: this env's velocity gain (the block's kd unless the kd channel drew)
@@ -665,7 +758,15 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
   const bool mp_on = DR && MODE == 1 && X.mp_on;      // a plate mass channel is on (wave-uniform): per-env plate inertia instead of plate_si / plate_phi
   const float m_plate = mp_on ? X.m_plate : 0.f, s_plate = mp_on ? X.s_plate : 0.f;
   M3 Rf = quat_to_mat(F.q.w, F.q.x, F.q.y, F.q.z);
-  constexpr bool REG0_ = LM_PASS0_REG ? REG0 != 0 : false;      // first pass on registers (else: both passes read the stash back, the form before round 5)
+#ifdef LM_HELPER_WAVE
+  static_assert(!HW || (MODE == 0 && !DR && LM_PASS0_REG && REG0), "the helper wavefront serves the un-randomised locomotion sub-step with its first pass on registers");
+  if (HW) {      // what the helper needs of this sub-step's state; it starts behind the barrier
+    St.put(HAND_IN, q[0], q[1], q[2], qd[0]); St.put(HAND_IN + 1, qd[1], qd[2], F.u.w.x, F.u.w.y); St.put(HAND_IN + 2, F.u.w.z, F.u.v.x, F.u.v.y, F.u.v.z);
+    St.put(HAND_IN + 3, Rf.c0.z, Rf.c1.z, Rf.c2.z, 0.f);
+    hw_barrier();
+  }
+#endif
+  constexpr bool REG0_ = LM_PASS0_REG ? REG0 != 0 : false;     // first pass on registers (else: both passes read the stash back, the form before round 5)
   // read with the sub-step's other parameters, not inside the divergent phi < 0 branch (a cache round trip on every wavefront with a penetrating
   // foot).  Not in the kernels that keep the stash form: two more live registers cost k_step_w2 20 B of scratch
   const float baumgarte = REG0_ ? P->baumgarte : 0.f, max_depen_vel = REG0_ ? P->max_depen_vel : 0.f;
@@ -677,6 +778,7 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
     LimbKin K; limb_kinematics(tl, q, qd, K);
     LimbDyn D;
     if (DR && X.mb_on) limb_dynamics<1>(tl, K, qd, v0, avp0, D, X.m_s, X.m_41, X.m_32);      // body-mass channel on (wave-uniform): per-env masses
+    else if (HW) limb_dynamics<0, 1>(tl, K, qd, v0, avp0, D);      // the inertia chain; fcs and hq: the helper wavefront's, fetched by the pass
     else limb_dynamics(tl, K, qd, v0, avp0, D);
     LM_STAMP(1);
     if (MODE == 0) {
@@ -694,7 +796,7 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
       const V3 com0 = (1.0f / I0.m) * I0.h;
       I0.m *= m0; I0.h = m0 * I0.h; I0.xx *= m0; I0.yy *= m0; I0.zz *= m0; I0.xy *= m0; I0.xz *= m0; I0.yz *= m0;
       D.Isc = D.Isc + I0;
-      D.fcs = D.fcs + I0 * avp0 + fcross(v0, I0 * v0);
+      if (!HW) D.fcs = D.fcs + I0 * avp0 + fcross(v0, I0 * v0);      // (HW: the helper wavefront adds the hub's bias term)
       if (DR) { V3 fh = m0 * mulT(Rb, X.f); D.fcs = D.fcs - sv(cross(com0, fh), fh); }      // randomised force on the base link, at its COM
     }
     // ---- contact geometry of this limb's tip
@@ -778,6 +880,11 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
 #endif
       }
     } else {
+#ifdef LM_HELPER_WAVE
+      if (HW) {      // the helper wavefront's terms: not in I (the first pass fetches them where it needs them, the second pass below)
+        D.fcs = sv(v3(0, 0, 0), v3(0, 0, 0)); D.hq[0] = D.hq[1] = D.hq[2] = 0.f;
+      }
+#endif
       I.Fq0 = s6(D.Fq0); I.Fq1 = s6(D.Fq1); I.Fq2 = s6(D.Fq2);
       I.Ha[0] = D.H[0]; I.Ha[1] = D.H[1]; I.Ha[2] = D.H[2]; I.Ha[3] = D.H[3]; I.Ha[4] = D.H[4]; I.Ha[5] = D.H[5];
       I.hq[0] = D.hq[0]; I.hq[1] = D.hq[1]; I.hq[2] = D.hq[2];
@@ -847,9 +954,16 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
   } else {
     // first pass: on the registers just computed.  Second pass: reloaded from the stash, under a wave-uniform branch; envs without saturation
     // redo the identical unsaturated solve in it (same result)
-    substep_pass<MODE, VAR, DR, CF>(P, limb, F, I, dt, kd, cjv, sat, tsat, tgt, qd, bn, mu_dr, mp_on, m_plate, s_plate, qdn, un, lamc);
+    substep_pass<MODE, VAR, DR, CF, HW>(P, limb, F, I, dt, kd, cjv, sat, tsat, tgt, qd, bn, mu_dr, mp_on, m_plate, s_plate, qdn, un, lamc, &St);
     if (second_pass_due()) {
       unstash_terms<MODE>(St, I);
+#ifdef LM_HELPER_WAVE
+      if (HW) {      // the helper's terms are still in its slots: it writes them again behind the next sub-step's first barrier
+        const float4 b0 = St.get(HAND_OUT), b1 = St.get(HAND_OUT + 1), b2 = St.get(HAND_OUT + 2);
+        I.PB[0].p.x = b0.x; I.PB[1].p.x = b0.y; I.PB[2].p.x = b0.z; I.PB[3].p.x = b0.w; I.PB[4].p.x = b1.x; I.PB[5].p.x = b1.y;
+        I.hq[0] = b1.z; I.hq[1] = b1.w; I.hq[2] = b2.x;
+      }
+#endif
       substep_pass<MODE, VAR, DR, CF>(P, limb, F, I, dt, kd, cjv, sat, tsat, tgt, qd, bn, mu_dr, mp_on, m_plate, s_plate, qdn, un, lamc);
     }
   }

@@ -515,6 +515,8 @@ static int fail(int code, const char* msg) { snprintf(g_err, sizeof(g_err), "%s"
 struct lm_engine {
   int N, n_tasks, split, nblocks, num_obs, device;
   int w2_min_envs;         // lm_step launches k_step_w2 (two wavefronts per SIMD) from this env count on; LM_W2_MIN_ENVS overrides 32769 (tests, A/B)
+  int h2_max_envs;         // lm_step launches k_step_h2 (a helper wavefront per workgroup) up to this env count: while 2 wavefronts per 16 envs find a SIMD each
+                           // (8192 envs on MI355X); LM_H2_MAX_ENVS overrides it (tests, A/B; 0 = never)
   uint32_t seed;
   lm_params* d_params;     // [2]
   float* d_table;
@@ -653,6 +655,16 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
   h->N = n_envs; h->n_tasks = n_tasks; h->split = (n_tasks == 2) ? split_env : n_envs; h->seed = seed;
   h->nblocks = (n_envs + ENVS_PER_WAVE - 1) / ENVS_PER_WAVE;
   { const char* e = getenv("LM_W2_MIN_ENVS"); h->w2_min_envs = e ? atoi(e) : 32769; }
+  {
+    // beyond one wavefront per SIMD a 128-thread workgroup costs a second generation of wavefronts: k_step / k_step_w2 from there on
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 0;
+    h->h2_max_envs = (4 * cus / 2) * ENVS_PER_WAVE;
+    if (const char* e = getenv("LM_H2_MAX_ENVS")) {      // a malformed or negative value is ignored
+      char* end = nullptr; const long v = strtol(e, &end, 10);
+      if (end != e && *end == '\0' && v >= 0 && v <= INT32_MAX) h->h2_max_envs = (int)v;
+    }
+  }
   h->num_obs = params[0].num_obs; h->dr_enabled = params[0].dr_enabled != 0;
   h->h_params[0] = params[0]; h->h_params[1] = params[n_tasks - 1];
   derive_params(&h->h_params[0]); derive_params(&h->h_params[1]);
@@ -737,6 +749,19 @@ static void drop_unrequested_views(const lm_engine* h, StepArgs& A) {
 extern "C" int lm_debug_stamps(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(lm_stamp_out), sizeof(lm_stamp_out)) == hipSuccess ? 0 : -1; }
 #endif
 
+// Which velocity-drive kernel lm_step launches on an engine without randomisation and contact reporting: 0 = k_step (one wavefront per 16 envs),
+// 1 = k_step_w2 (two such workgroups per SIMD: locomotion-only engines from w2_min_envs on), 2 = k_step_h2 (a helper wavefront beside each:
+// engines with a locomotion block up to h2_max_envs).  Every other engine: 0, the one-wavefront kernel of its family.
+static int step_variant(const lm_engine* h) {
+  const int k0 = h->h_params[0].variant * 2 + (h->h_params[0].mode == LM_MODE_MANI ? 1 : 0), k1 = h->h_params[1].variant * 2 + (h->h_params[1].mode == LM_MODE_MANI ? 1 : 0);
+  if (h->contact_on || h->dr_enabled || k0 >= 2 || k1 >= 2) return 0;
+  if (k0 == 0 && k1 == 0 && h->N >= h->w2_min_envs) return 1;
+  if ((k0 == 0 || k1 == 0) && h->N <= h->h2_max_envs) return 2;
+  return 0;
+}
+// (not part of the C ABI: for tests and A/B runs that must know which kernel ran; -1 without an engine)
+int lm_internal_step_variant(const lm_engine* h) { return h ? step_variant(h) : -1; }
+
 int lm_step(lm_engine* h, const float* actions, const float* goal_rand, float* out_obs, float* out_states, float* out_rew,
             int64_t* out_resets, float* out_extras, void* stream) {
   if (!h || !actions) return fail(LM_EINVAL, "lm_step: null handle or actions");
@@ -745,7 +770,9 @@ int lm_step(lm_engine* h, const float* actions, const float* goal_rand, float* o
   StepArgs A = make_args(h, actions, goal_rand, out_obs, out_states, out_rew, out_resets); A.W.out_extras = out_extras;
   drop_unrequested_views(h, A);
   const bool pd = A.kind[0] >= 2;                                  // both blocks are of one actuator family (lm_create)
-  if (!h->contact_on && !h->dr_enabled && A.kind[0] == 0 && A.kind[1] == 0 && h->N >= h->w2_min_envs) lm_internal_launch_step_w2(&A, h->nblocks, s);      // locomotion, two wavefronts per SIMD: ahead beyond 32 768 envs
+  const int variant = step_variant(h);
+  if (variant == 1) lm_internal_launch_step_w2(&A, h->nblocks, s);      // locomotion, two wavefronts per SIMD: ahead beyond 32 768 envs
+  else if (variant == 2) lm_internal_launch_step_h2(&A, h->nblocks, s);      // a helper wavefront per workgroup: ahead while half the SIMDs are idle
   else {
     void (*kern)(StepArgs) = h->contact_on ? (h->dr_enabled ? (pd ? k_step_dr_pd_cf : k_step_dr_cf) : (pd ? k_step_pd_cf : k_step_cf))      // with reporting: one-wavefront kernels at every size
                                            : (h->dr_enabled ? (pd ? k_step_dr_pd : k_step_dr) : (pd ? k_step_pd : k_step));

@@ -45,10 +45,12 @@ struct StepArgs {
                                     // step used (the randomised kernels only; the new last member)
 };
 extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_w2(const StepArgs* A, int nblocks, hipStream_t s);      // k_step_w2's launcher (lm_engine_w2.hip), called by lm_step
+extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_h2(const StepArgs* A, int nblocks, hipStream_t s);      // k_step_h2's launcher (lm_engine_h2.hip), called by lm_step
 
 // REG0: substep()'s first drive pass runs on registers (1, the step kernels) or reads the stash back like the second (0: k_step_w2 and the
 // persistent rollouts, whose register budget has no room for it; same arithmetic, same bits)
-template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0, int REG0 = 1>
+// HW: wavefront 0 of k_step_h2, whose helper wavefront computes the limb bias terms of every sub-step (helper_wave, lm_dynamics.h)
+template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0, int REG0 = 1, int HW = 0>
 LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float* sTab, float* sObs, float* sSt, float4* sStash) {
   TableRegs TR; table_fetch(A.table, threadIdx.x, TR);
   const int lane = threadIdx.x, limb = lane & 3, envl = lane >> 2;
@@ -239,7 +241,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
     const bool posm = P->drive_mode == LM_DRIVE_POSITION; const float gp = posm ? (DR ? X.gk : P->pd_kp / P->kd) : 0.f;
     for (int s = 0; s < nsub; s++) {
       const float tgt[3] = {posm ? gp * (a0[0] - q[0]) : a0[0], posm ? gp * (a0[1] - q[1]) : a0[1], posm ? gp * (a0[2] - q[2]) : a0[2]};
-      substep<MODE, VAR, DR, CF, REG0>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X, cf);
+      substep<MODE, VAR, DR, CF, REG0, HW>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X, cf);
     }
   } else {
     // ---- custom-controller tasks (quadruped_pose_control_custom_controller.py:255-307): the action integrates the swing / extension
@@ -265,7 +267,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
       if (s == nsub - P->acc_substeps) { qda[0] = qd[0]; qda[1] = qd[1]; qda[2] = qd[2]; qda_set = true; }
       const bool prev = lat_on && s < X.lat;
       float tgt[3] = {g * ((prev ? tgtp[0] : tgtq[0]) - q[0]), g * ((prev ? tgtp[1] : tgtq[1]) - q[1]), g * ((prev ? tgtp[2] : tgtq[2]) - q[2])};
-      substep<MODE, VAR, DR, CF, REG0>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X, cf);
+      substep<MODE, VAR, DR, CF, REG0, HW>(P, sTab, tl, limb, St, F, Rfix, pfix, q, qd, tgt, tau_acc, X, cf);
     }
   }
   if (CF) store_contact(A.contact, N, env, limb, active, cf, nsub, P->dt);      // nsub = 0 (lm_post_physics): the record is left as it was
