@@ -308,7 +308,9 @@ int lm_enable_contact_forces(lm_engine* h, int on);
  * wavefronts per SIMD (k_step_w2: same bits, faster beyond two generations of workgroups; the environment variable LM_W2_MIN_ENVS, read
  * by lm_create, moves that threshold).  Un-randomised velocity-drive engines with a locomotion block, small enough that two wavefronts per
  * 16 envs still find a SIMD each (8192 envs on MI355X), get the kernel with a helper wavefront per workgroup (k_step_h2: same bits; the
- * environment variable LM_H2_MAX_ENVS, read by lm_create, moves that threshold, 0 = never). */
+ * environment variable LM_H2_MAX_ENVS, read by lm_create, moves that threshold, 0 = never).  Up to one workgroup per compute unit
+ * (4096 envs on MI355X) the same engines get the kernel with two helper wavefronts (k_step_h3: same bits; LM_H3_MAX_ENVS moves that
+ * threshold, 0 = never; with only LM_H2_MAX_ENVS set it is off). */
 int lm_step(lm_engine* h, const float* actions, const float* goal_rand, float* out_obs, float* out_states,
             float* out_rew, int64_t* out_resets, float* out_extras, void* stream);
 

@@ -394,9 +394,11 @@ LM_DEV void integrate_free(FreeBody& F, const M3& R, float dt) {
 #define LM_STEP_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
 #elif defined(LM_HELPER_WAVE)
 // k_step_h2 (lm_engine_h2.hip): a second wavefront of the workgroup computes the limb bias terms (see helper_wave below).  The two wavefronts
-// exchange 16 + 9 floats per lane and sub-step through seven more slots of the same [slot][lane] array
+// exchange 16 + 9 floats per lane and sub-step through seven more slots of the same [slot][lane] array.  k_step_h3 (lm_engine_h3.hip,
+// LM_HELPER_WAVE 2) has a third wavefront for the contact terms (helper_wave_terms): it reads the same four slots, with the base height in
+// the last word, and writes stash slots 7-15 themselves
 #define STASH_SLOTS 29
-#define HAND_IN 22            // 4 slots, wavefront 0 -> helper: q, qd | qd, u.w | u.w, u.v | row 2 of the base's rotation
+#define HAND_IN 22            // 4 slots, wavefront 0 -> helpers: q, qd | qd, u.w | u.w, u.v | row 2 of the base's rotation (k_step_h3: and the base height)
 #define HAND_OUT 26           // 3 slots, helper -> wavefront 0: fcs | fcs, hq | hq
 #define LM_STEP_ATTR
 #else
@@ -491,6 +493,21 @@ template <int MODE> LM_DEV void stash_terms(const Stash& St, const PassTerms& I)
 #endif
   }
 }
+#ifdef LM_HELPER_WAVE
+// k_step_h3's wavefront 0 computes, pins and stashes the inertia chain's terms only (MODE 0: slots 0-6 with hq zero, 16-18); slots 7-15 are
+// written by the terms helper (helper_wave_terms)
+LM_DEV void pin_chain(PassTerms& I) {
+  pin(I.Fq0); pin(I.Fq1); pin(I.Fq2);
+  pin(I.Ha[0]); pin(I.Ha[1]); pin(I.Ha[2]); pin(I.Ha[3]); pin(I.Ha[4]); pin(I.Ha[5]);
+  pin(I.Isc.m); pin(I.Isc.h.x); pin(I.Isc.h.y); pin(I.Isc.h.z); pin(I.Isc.xx); pin(I.Isc.yy); pin(I.Isc.zz); pin(I.Isc.xy); pin(I.Isc.xz); pin(I.Isc.yz);
+}
+LM_DEV void stash_chain(const Stash& St, const PassTerms& I) {
+  put2(St, 0, I.Fq0.a, I.Fq0.b); put2(St, 1, I.Fq0.c, I.Fq1.a); put2(St, 2, I.Fq1.b, I.Fq1.c); put2(St, 3, I.Fq2.a, I.Fq2.b);
+  St.put(4, I.Fq2.c.x, I.Fq2.c.y, 0.f, 0.f);
+  St.put(5, I.Ha[0], I.Ha[1], I.Ha[2], I.Ha[3]); St.put(6, I.Ha[4], I.Ha[5], 0.f, 0.f);
+  St.put(16, I.Isc.m, I.Isc.h.x, I.Isc.h.y, I.Isc.h.z); St.put(17, I.Isc.xx, I.Isc.yy, I.Isc.zz, I.Isc.xy); St.put(18, I.Isc.xz, I.Isc.yz, 0.f, 0.f);
+}
+#endif
 template <int MODE> LM_DEV void unstash_terms(const Stash& St, PassTerms& I) {
   asm volatile("" ::: "memory");          // keep the stash reloads where the pass that needs them starts (no hoisting across the PGS loop)
   float isc_xz = 0.f, isc_yz = 0.f;
@@ -548,6 +565,8 @@ LM_DEV SI plate_inertia_env(const lm_params* __restrict__ P, float m, float s) {
 // HW 1 (the first pass of wavefront 0 of k_step_h2): I.hq and the bias halves PB[i].p.x are not in I; the pass fetches them from the helper
 // wavefront's slots (Hd) behind its second barrier, which stands where they are first needed - after the articulated hub inertia, so that
 // wavefront 0 has more work before the barrier than the helper has and does not wait there.
+// HW 2 (the first pass of wavefront 0 of k_step_h3): as HW 1, and Jq, the hub rows PB[i].p.y / PB[i].q and bn are not in I / bn either; the pass
+// reads them behind the same barrier from stash slots 7-15, where the terms helper (helper_wave_terms) has written them.
 template <int MODE, int VAR, int DR, int CF, int HW = 0>
 LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBody& F, const PassTerms& I, float dt, float kd, const float cjv[3],
                          const bool sat[3], const float tsat[3], const float tgt[3], const float qd[3], float bn, float mu_dr,
@@ -556,8 +575,11 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
   float Ha[6] = {I.Ha[0], I.Ha[1], I.Ha[2], I.Ha[3], I.Ha[4], I.Ha[5]}, r[3];
   const float hq[3] = {I.hq[0], I.hq[1], I.hq[2]};
   R4 PBh[6];      // HW: the rows with the helper's bias wrench
-  const float Jq[3][3] = {{I.Jq0[0], I.Jq0[1], I.Jq0[2]}, {I.j12[0].x, I.j12[1].x, I.j12[2].x}, {I.j12[0].y, I.j12[1].y, I.j12[2].y}};
-  const f2 j12[3] = {I.j12[0], I.j12[1], I.j12[2]};      // (Jq[1][c] | Jq[2][c])
+  const float Jq_[3][3] = {{I.Jq0[0], I.Jq0[1], I.Jq0[2]}, {I.j12[0].x, I.j12[1].x, I.j12[2].x}, {I.j12[0].y, I.j12[1].y, I.j12[2].y}};
+  const f2 j12_[3] = {I.j12[0], I.j12[1], I.j12[2]};      // (Jq[1][c] | Jq[2][c])
+  float Jqh[3][3]; f2 j12h[3]; float bnh = bn;      // HW 2: the terms helper's, fetched behind the barrier
+  const float (*Jq)[3] = HW == 2 ? Jqh : Jq_;
+  const f2* j12 = HW == 2 ? j12h : j12_;
   const R4* PB = HW ? PBh : I.PB;
   const int di[3] = {0, 3, 5};
 #pragma unroll
@@ -601,8 +623,23 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
       hw_barrier();      // the helper's second barrier of the sub-step: its bias terms are in LDS
       const float4 b0 = Hd->get(HAND_OUT), b1 = Hd->get(HAND_OUT + 1), b2 = Hd->get(HAND_OUT + 2);
       const float fcs[6] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y}, hqh[3] = {b1.z, b1.w, b2.x};
+      if (HW == 2) {
+        // k_step_h3: the contact rows and the approach rate are the terms helper's (helper_wave_terms), in the stash slots the second pass
+        // reads them from.  Read back from LDS they are what pin_terms made of them in k_step: values no expression is contracted with
+        const float4 t7 = Hd->get(7), t8 = Hd->get(8), t9 = Hd->get(9);
+        const float4 g0 = Hd->get(10), g1 = Hd->get(11), g2 = Hd->get(12), g3 = Hd->get(13), g4 = Hd->get(14), g5 = Hd->get(15);
+        j12h[0] = mk2(t8.x, t8.y); j12h[1] = mk2(t8.z, t8.w); j12h[2] = mk2(t9.x, t9.y); bnh = t9.z;
+        Jqh[0][0] = t7.y; Jqh[0][1] = t7.z; Jqh[0][2] = t7.w;
+#pragma unroll
+        for (int c = 0; c < 3; c++) { Jqh[1][c] = j12h[c].x; Jqh[2][c] = j12h[c].y; }
+        PBh[0].p = mk2(fcs[0], g0.y); PBh[1].p = mk2(fcs[1], g0.w); PBh[2].p = mk2(fcs[2], g1.y);
+        PBh[3].p = mk2(fcs[3], g1.w); PBh[4].p = mk2(fcs[4], g2.y); PBh[5].p = mk2(fcs[5], g2.w);
+        PBh[0].q = mk2(g3.x, g3.y); PBh[1].q = mk2(g3.z, g3.w); PBh[2].q = mk2(g4.x, g4.y);
+        PBh[3].q = mk2(g4.z, g4.w); PBh[4].q = mk2(g5.x, g5.y); PBh[5].q = mk2(g5.z, g5.w);
+      } else {
 #pragma unroll
       for (int i = 0; i < 6; i++) { PBh[i].p = mk2(fcs[i], I.PB[i].p.y); PBh[i].q = I.PB[i].q; }
+      }
 #pragma unroll
       for (int a = 0; a < 3; a++) {
 #pragma clang fp contract(off)
@@ -681,7 +718,7 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
   }
   float lam[3], w[6];
   LM_STAMP(3);
-  PgsState S; pgs_setup(S, limb, DR ? mu_dr : P->mu, bn, vf, Wl, T, X);
+  PgsState S; pgs_setup(S, limb, DR ? mu_dr : P->mu, HW == 2 ? bnh : bn, vf, Wl, T, X);
   pgs_sweeps(S, 0, P->pgs_iters);
   pgs_finish(S, DR ? mu_dr : P->mu, X, lam, w);
   if (CF) { lamc[0] = lam[0]; lamc[1] = lam[1]; lamc[2] = lam[2]; }
@@ -741,6 +778,48 @@ LM_DEV void helper_wave(const lm_params* __restrict__ P, const float* sTab, floa
     hw_barrier();      // the bias terms are in LDS
   }
 }
+#if LM_HELPER_WAVE >= 2
+// The terms helper of k_step_h3 (threads 128-191; lane l serves lane l of wavefront 0), a third wavefront on a third SIMD.  Between the same
+// two barriers as helper_wave it recomputes the limb kinematics, takes the foot selects of limb_dynamics<0, 1> (its inertia chain is dead here
+// and compiled away) and runs the locomotion branch of substep()'s contact geometry: the contact axes, the gap and the approach rate bn, the
+// nine Jq dots and the three hub rows - the lines substep() compiles, on inputs that k_step holds rounded in registers too (row 2 of the
+// base's rotation is only ever a factor, the base height is loop-carried state).  It writes them where stash_terms puts them, slots 7-15 with
+// the bias halves zero as wavefront 0 of k_step_h2 leaves them, and bn in the spare half of slot 9.  Wavefront 0 reads the slots behind the
+// second barrier (substep_pass, HW 2) and a second pass reads them again (unstash_terms); this wavefront writes them again only behind the
+// next sub-step's first barrier, which wavefront 0 reaches with its LDS reads complete.  Same barrier discipline as helper_wave.
+LM_DEV void helper_wave_terms(const lm_params* __restrict__ P, const float* sTab, float4* sStash, int lane, int nsub) {
+  const int limb = lane & 3;
+  const float* tl = sTab + HUB_FLOATS + limb * LIMB_STRIDE;
+  Stash St; St.base = sStash; St.lane = lane;
+  const float dt = P->dt, baumgarte = P->baumgarte, max_depen_vel = P->max_depen_vel;
+  for (int s = 0; s < nsub; s++) {
+    hw_barrier();      // the joint state of this sub-step is published
+    const float4 h0 = St.get(HAND_IN), h1 = St.get(HAND_IN + 1), h2 = St.get(HAND_IN + 2), h3 = St.get(HAND_IN + 3);
+    const float q[3] = {h0.x, h0.y, h0.z}, qd[3] = {h0.w, h1.x, h1.y};
+    const SV v0 = sv(v3(h1.z, h1.w, h2.x), v3(h2.y, h2.z, h2.w));
+    const SV avp0 = sv(v3(0, 0, 0), v3(0, 0, 0));      // (feeds the bias chain only)
+    LimbKin K; limb_kinematics(tl, q, qd, K);
+    LimbDyn D; limb_dynamics<0, 1>(tl, K, qd, v0, avp0, D);
+    // ---- contact geometry of this limb's tip, as in substep() (MODE 0)
+    V3 C0, C1, C2; float phi;
+    C0 = v3(h3.x, h3.y, h3.z);
+    C1 = rsqrtf(fmaxf(1.0f - C0.x * C0.x, 1.0e-12f)) * v3(1.0f - C0.x * C0.x, -C0.x * C0.y, -C0.x * C0.z);
+    C2 = cross(C0, C1);
+    phi = h3.w + dot(C0, D.x) - P->tip_radius;
+    D.x = fma3(-P->tip_radius, C0, D.x);
+    const float bn = (phi >= 0.f) ? phi / dt : fmaxf(baumgarte * phi / dt, -max_depen_vel);
+    V3 e0 = K.s1.v + cross(K.s1.w, D.x);
+    V3 e1 = D.j31.v + cross(D.j31.w, D.x);
+    V3 e2 = D.j32.v + cross(D.j32.w, D.x);
+    St.put(7, 0.f, dot(C0, e0), dot(C0, e1), dot(C0, e2));
+    St.put(8, dot(C1, e0), dot(C2, e0), dot(C1, e1), dot(C2, e1)); St.put(9, dot(C1, e2), dot(C2, e2), bn, 0.f);
+    const V3 n0 = cross(D.x, C0), n1 = cross(D.x, C1), n2 = cross(D.x, C2);
+    St.put(10, 0.f, n0.x, 0.f, n0.y); St.put(11, 0.f, n0.z, 0.f, C0.x); St.put(12, 0.f, C0.y, 0.f, C0.z);
+    St.put(13, n1.x, n2.x, n1.y, n2.y); St.put(14, n1.z, n2.z, C1.x, C2.x); St.put(15, C1.y, C2.y, C1.z, C2.z);
+    hw_barrier();      // the contact terms are in LDS
+  }
+}
+#endif
 #endif
 
 // One physics sub-step of one env (4 lanes).  MODE 0: F is the robot base.  MODE 1: F is the plate, the
@@ -762,7 +841,7 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
   static_assert(!HW || (MODE == 0 && !DR && LM_PASS0_REG && REG0), "the helper wavefront serves the un-randomised locomotion sub-step with its first pass on registers");
   if (HW) {      // what the helper needs of this sub-step's state; it starts behind the barrier
     St.put(HAND_IN, q[0], q[1], q[2], qd[0]); St.put(HAND_IN + 1, qd[1], qd[2], F.u.w.x, F.u.w.y); St.put(HAND_IN + 2, F.u.w.z, F.u.v.x, F.u.v.y, F.u.v.z);
-    St.put(HAND_IN + 3, Rf.c0.z, Rf.c1.z, Rf.c2.z, 0.f);
+    St.put(HAND_IN + 3, Rf.c0.z, Rf.c1.z, Rf.c2.z, HW == 2 ? F.p.z : 0.f);      // (HW 2: the base height, for the terms helper's gap)
     hw_barrier();
   }
 #endif
@@ -799,6 +878,22 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
       if (!HW) D.fcs = D.fcs + I0 * avp0 + fcross(v0, I0 * v0);      // (HW: the helper wavefront adds the hub's bias term)
       if (DR) { V3 fh = m0 * mulT(Rb, X.f); D.fcs = D.fcs - sv(cross(com0, fh), fh); }      // randomised force on the base link, at its COM
     }
+#ifdef LM_HELPER_WAVE
+    if (HW == 2) {
+      // k_step_h3: the inertia chain's terms only.  The contact geometry, the Jq dots and the hub rows are the terms helper's
+      // (helper_wave_terms): the first pass reads them from stash slots 7-15 behind its barrier, and so does a second pass
+      I.Fq0 = s6(D.Fq0); I.Fq1 = s6(D.Fq1); I.Fq2 = s6(D.Fq2);
+      I.Ha[0] = D.H[0]; I.Ha[1] = D.H[1]; I.Ha[2] = D.H[2]; I.Ha[3] = D.H[3]; I.Ha[4] = D.H[4]; I.Ha[5] = D.H[5];
+      I.hq[0] = I.hq[1] = I.hq[2] = 0.f; I.Jq0[0] = I.Jq0[1] = I.Jq0[2] = 0.f; I.j12[0] = I.j12[1] = I.j12[2] = sp2(0.f);
+#pragma unroll
+      for (int i = 0; i < 6; i++) { I.PB[i].p = sp2(0.f); I.PB[i].q = sp2(0.f); }
+      I.Isc = D.Isc;
+      pin_chain(I);
+      stash_chain(St, I);
+      bn = 0.f;
+    }
+#endif
+    if (HW != 2) {
     // ---- contact geometry of this limb's tip
     V3 C0, C1, C2;        // contact axes (n, t1, t2) in hub coordinates
     float phi;
@@ -901,6 +996,7 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
       pin_terms<MODE>(I);
       stash_terms<MODE>(St, I);
     }
+    }
   }
 
   LM_STAMP(2);
@@ -962,6 +1058,7 @@ LM_DEV void substep(const lm_params* __restrict__ P, const float* th, const floa
         const float4 b0 = St.get(HAND_OUT), b1 = St.get(HAND_OUT + 1), b2 = St.get(HAND_OUT + 2);
         I.PB[0].p.x = b0.x; I.PB[1].p.x = b0.y; I.PB[2].p.x = b0.z; I.PB[3].p.x = b0.w; I.PB[4].p.x = b1.x; I.PB[5].p.x = b1.y;
         I.hq[0] = b1.z; I.hq[1] = b1.w; I.hq[2] = b2.x;
+        if (HW == 2) bn = St.get(9).z;      // the terms helper's approach rate rides in the spare half of slot 9
       }
 #endif
       substep_pass<MODE, VAR, DR, CF>(P, limb, F, I, dt, kd, cjv, sat, tsat, tgt, qd, bn, mu_dr, mp_on, m_plate, s_plate, qdn, un, lamc);

@@ -517,6 +517,9 @@ struct lm_engine {
   int w2_min_envs;         // lm_step launches k_step_w2 (two wavefronts per SIMD) from this env count on; LM_W2_MIN_ENVS overrides 32769 (tests, A/B)
   int h2_max_envs;         // lm_step launches k_step_h2 (a helper wavefront per workgroup) up to this env count: while 2 wavefronts per 16 envs find a SIMD each
                            // (8192 envs on MI355X); LM_H2_MAX_ENVS overrides it (tests, A/B; 0 = never)
+  int h3_max_envs;         // ... and k_step_h3 (two helper wavefronts per workgroup) up to this one: one workgroup per CU (4096 envs on MI355X: a wavefront of
+                           // 466 registers has a SIMD to itself, so a second workgroup of three finds no room on a CU and waits for a second generation -
+                           // measured at 5456 envs: 54.2 against k_step_h2's 31.7 us); LM_H3_MAX_ENVS overrides it; off when only LM_H2_MAX_ENVS is set (that forces k_step_h2 or k_step)
   uint32_t seed;
   lm_params* d_params;     // [2]
   float* d_table;
@@ -664,6 +667,11 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
       char* end = nullptr; const long v = strtol(e, &end, 10);
       if (end != e && *end == '\0' && v >= 0 && v <= INT32_MAX) h->h2_max_envs = (int)v;
     }
+    h->h3_max_envs = getenv("LM_H2_MAX_ENVS") ? 0 : cus * ENVS_PER_WAVE;
+    if (const char* e = getenv("LM_H3_MAX_ENVS")) {      // a malformed or negative value is ignored
+      char* end = nullptr; const long v = strtol(e, &end, 10);
+      if (end != e && *end == '\0' && v >= 0 && v <= INT32_MAX) h->h3_max_envs = (int)v;
+    }
   }
   h->num_obs = params[0].num_obs; h->dr_enabled = params[0].dr_enabled != 0;
   h->h_params[0] = params[0]; h->h_params[1] = params[n_tasks - 1];
@@ -751,11 +759,13 @@ extern "C" int lm_debug_stamps(unsigned long long* out) { return hipMemcpyFromSy
 
 // Which velocity-drive kernel lm_step launches on an engine without randomisation and contact reporting: 0 = k_step (one wavefront per 16 envs),
 // 1 = k_step_w2 (two such workgroups per SIMD: locomotion-only engines from w2_min_envs on), 2 = k_step_h2 (a helper wavefront beside each:
-// engines with a locomotion block up to h2_max_envs).  Every other engine: 0, the one-wavefront kernel of its family.
+// engines with a locomotion block up to h2_max_envs), 3 = k_step_h3 (two helper wavefronts: the same engines up to h3_max_envs).  Every other
+// engine: 0, the one-wavefront kernel of its family.
 static int step_variant(const lm_engine* h) {
   const int k0 = h->h_params[0].variant * 2 + (h->h_params[0].mode == LM_MODE_MANI ? 1 : 0), k1 = h->h_params[1].variant * 2 + (h->h_params[1].mode == LM_MODE_MANI ? 1 : 0);
   if (h->contact_on || h->dr_enabled || k0 >= 2 || k1 >= 2) return 0;
   if (k0 == 0 && k1 == 0 && h->N >= h->w2_min_envs) return 1;
+  if ((k0 == 0 || k1 == 0) && h->N <= h->h3_max_envs) return 3;
   if ((k0 == 0 || k1 == 0) && h->N <= h->h2_max_envs) return 2;
   return 0;
 }
@@ -772,6 +782,7 @@ int lm_step(lm_engine* h, const float* actions, const float* goal_rand, float* o
   const bool pd = A.kind[0] >= 2;                                  // both blocks are of one actuator family (lm_create)
   const int variant = step_variant(h);
   if (variant == 1) lm_internal_launch_step_w2(&A, h->nblocks, s);      // locomotion, two wavefronts per SIMD: ahead beyond 32 768 envs
+  else if (variant == 3) lm_internal_launch_step_h3(&A, h->nblocks, s);      // two helper wavefronts per workgroup: ahead up to one workgroup per CU
   else if (variant == 2) lm_internal_launch_step_h2(&A, h->nblocks, s);      // a helper wavefront per workgroup: ahead while half the SIMDs are idle
   else {
     void (*kern)(StepArgs) = h->contact_on ? (h->dr_enabled ? (pd ? k_step_dr_pd_cf : k_step_dr_cf) : (pd ? k_step_pd_cf : k_step_cf))      // with reporting: one-wavefront kernels at every size

@@ -46,11 +46,14 @@ struct StepArgs {
 };
 extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_w2(const StepArgs* A, int nblocks, hipStream_t s);      // k_step_w2's launcher (lm_engine_w2.hip), called by lm_step
 extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_h2(const StepArgs* A, int nblocks, hipStream_t s);      // k_step_h2's launcher (lm_engine_h2.hip), called by lm_step
+extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_h3(const StepArgs* A, int nblocks, hipStream_t s);      // k_step_h3's launcher (lm_engine_h3.hip), called by lm_step
 
 // REG0: substep()'s first drive pass runs on registers (1, the step kernels) or reads the stash back like the second (0: k_step_w2 and the
 // persistent rollouts, whose register budget has no room for it; same arithmetic, same bits)
 // HW: wavefront 0 of k_step_h2, whose helper wavefront computes the limb bias terms of every sub-step (helper_wave, lm_dynamics.h)
-template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0, int REG0 = 1, int HW = 0>
+// (HW 2: wavefront 0 of k_step_h3, whose second helper computes the contact terms too: helper_wave_terms.)  OW: that helper also streams the
+// staged obs / states of a full wavefront out (write_outputs, helper_write_outputs)
+template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0, int REG0 = 1, int HW = 0, int OW = 0>
 LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float* sTab, float* sObs, float* sSt, float4* sStash) {
   TableRegs TR; table_fetch(A.table, threadIdx.x, TR);
   const int lane = threadIdx.x, limb = lane & 3, envl = lane >> 2;
@@ -369,7 +372,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
   DO.sKey = reinterpret_cast<uint32_t*>(sStash);      // the stash is dead after the last sub-step
 #endif
   LM_STAMP(8);      // state stores issued
-  write_outputs<DR, DEFER, (VAR == 1) ? LM_MAX_OBS : 64>(P, A.W, N, env0, lane, limb, env, active, S, O, cnt, episode, sObs, sSt, DO);
+  write_outputs<DR, DEFER, (VAR == 1) ? LM_MAX_OBS : 64, OW>(P, A.W, N, env0, lane, limb, env, active, S, O, cnt, episode, sObs, sSt, DO);
   LM_STAMP(10);     // the reduction's round trips
 }
 

@@ -183,7 +183,50 @@ LM_DEV void publish_extra(const lm_params* __restrict__ P, const OutPtrs& W, int
 
 struct DrOut { int64_t* drc; uint32_t seed, dr_step; int64_t rand_buf, reset_key; uint32_t* sKey; };      // sKey: LDS [16][2] {corr key, fire}
 
-template <int DR, int DEFER = 0, int NOBS = 0>      // DEFER 1: only accumulate; the extras of this step are published later (persistent rollout kernel); NOBS 0: width from the parameters
+#ifdef LM_HELPER_WAVE
+// Whether a wavefront's outputs go out as whole float4 blocks: 16 envs and a 16-byte aligned out_states.  Wave-uniform, from kernel arguments only
+LM_DEV bool outputs_full(const OutPtrs& W, int N, int env0) {
+  return (min(ENVS_PER_WAVE, N - env0) == ENVS_PER_WAVE) && (reinterpret_cast<uintptr_t>(W.out_states) & 15) == 0;
+}
+// k_step_h3 (OW): the staged obs and states of a full wavefront without observation noise leave on the terms helper wavefront, behind the one
+// workgroup barrier wavefront 0 passes where write_outputs has its staging wait.  The loop is write_outputs' full-wavefront streaming path:
+// plain copies and clamps of what wavefront 0 staged in LDS, so the same bits.  Otherwise the helper only passes the barrier
+template <int NB>
+LM_DEV void helper_write_outputs(const lm_params* __restrict__ P, const OutPtrs& W, int N, int env0, int lane, const float* sObs, const float* sSt) {
+  hw_barrier();      // wavefront 0's staging writes are in LDS
+  if (!outputs_full(W, N, env0)) return;
+  const float clip = P->clip_obs;
+  auto clamp4 = [&](float4 v) { v.x = clampf(v.x, clip); v.y = clampf(v.y, clip); v.z = clampf(v.z, clip); v.w = clampf(v.w, clip); return v; };
+  constexpr int NV = ENVS_PER_WAVE * NB / 4, NS = ENVS_PER_WAVE * 93 / 4, KV = (NV + 63) / 64, KS = (NS + 63) / 64;
+  float4 vo[KV], vs[KS];
+#pragma unroll
+  for (int k = 0; k < KV; k++) { const int i = lane + 64 * k; vo[k] = reinterpret_cast<const float4*>(sObs)[(NV % 64 == 0 || i < NV) ? i : 0]; }
+#pragma unroll
+  for (int k = 0; k < KS; k++) { const int i = lane + 64 * k; vs[k] = reinterpret_cast<const float4*>(sSt)[(NS % 64 == 0 || i < NS) ? i : 0]; }
+  float4* ob = reinterpret_cast<float4*>(W.obs_buf + (size_t)env0 * NB); float4* oo = reinterpret_cast<float4*>(W.out_obs + (size_t)env0 * NB);
+  float4* sb = reinterpret_cast<float4*>(W.states_buf + (size_t)env0 * 93); float4* so = reinterpret_cast<float4*>(W.out_states + (size_t)env0 * 93);
+  if (W.out_obs) {
+#pragma unroll
+    for (int k = 0; k < KV; k++) { const int i = lane + 64 * k; if (NV % 64 == 0 || i < NV) oo[i] = clamp4(vo[k]); }
+  }
+  if (W.out_states) {
+#pragma unroll
+    for (int k = 0; k < KS; k++) { const int i = lane + 64 * k; if (NS % 64 == 0 || i < NS) so[i] = clamp4(vs[k]); }
+  }
+  if (W.obs_buf) {
+#pragma unroll
+    for (int k = 0; k < KV; k++) { const int i = lane + 64 * k; if (NV % 64 == 0 || i < NV) ob[i] = vo[k]; }
+  }
+  if (W.states_buf) {
+#pragma unroll
+    for (int k = 0; k < KS; k++) { const int i = lane + 64 * k; if (NS % 64 == 0 || i < NS) sb[i] = vs[k]; }
+  }
+}
+#endif
+
+// OW 1 (wavefront 0 of k_step_h3): the staging wait is a workgroup barrier, and the full-wavefront streaming loop runs on the terms helper
+// wavefront (helper_write_outputs)
+template <int DR, int DEFER = 0, int NOBS = 0, int OW = 0>      // DEFER 1: only accumulate; the extras of this step are published later (persistent rollout kernel); NOBS 0: width from the parameters
 LM_DEV void write_outputs(const lm_params* __restrict__ P, const OutPtrs& W, int N, int env0, int lane, int limb, int env, bool active,
                           const TaskState& S, const TaskOut& O, int64_t* cnt, int episode, float* sObs, float* sSt, const DrOut& DO) {
   if (DR) {
@@ -199,8 +242,14 @@ LM_DEV void write_outputs(const lm_params* __restrict__ P, const OutPtrs& W, int
       DO.drc[3 * (size_t)N + env] = DO.rand_buf + 1; DO.drc[4 * (size_t)N + env] = DO.reset_key;
     }
   }
+#ifdef LM_HELPER_WAVE
+  if (OW) hw_barrier();      // the staging writes landed, and the helper wavefront that streams them out may start
+  else
+#endif
+  {
   __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): LDS staging writes landed (single wave per block)
   __builtin_amdgcn_wave_barrier();
+  }
   // per-block partial sums in a fixed order (deterministic means).  Every lane of a quad holds its env's terms; lane 3 is the one that counts
   float tot0[12];
   {
@@ -243,7 +292,9 @@ LM_DEV void write_outputs(const lm_params* __restrict__ P, const OutPtrs& W, int
   const int NO = NOBS ? NOBS : P->num_obs;
   auto clamp4 = [&](float4 v) { v.x = clampf(v.x, clip); v.y = clampf(v.y, clip); v.z = clampf(v.z, clip); v.w = clampf(v.w, clip); return v; };
   const bool full = (nenv == ENVS_PER_WAVE) && (reinterpret_cast<uintptr_t>(W.out_states) & 15) == 0;
-  if (!DR && NOBS && full) {
+  if (OW && !DR && NOBS && full) {
+    // (k_step_h3: the terms helper wavefront streams the staging out, helper_write_outputs)
+  } else if (!DR && NOBS && full) {
     // a full wavefront without observation noise: 16 rows of obs (NOBS floats, a multiple of 4) and of states (93 floats; env0 is a multiple
     // of 16: 5952-byte offsets) are contiguous blocks of float4.  Known trip counts: all LDS reads are issued before the first store
     constexpr int NB = NOBS ? NOBS : 64, NV = ENVS_PER_WAVE * NB / 4, NS = ENVS_PER_WAVE * 93 / 4, KV = (NV + 63) / 64, KS = (NS + 63) / 64;

@@ -207,7 +207,7 @@ def hipcc_command(extra, out):
     # -amdgpu-mfma-vgpr-form: the MFMA accumulators of the policy tiles live in ordinary VGPRs, so the VALU work on them (ELU, max aggregation,
     # LDS stores) needs no v_accvgpr_read per element (504 of them in k_gnn_forward)
     return [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
-            "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_h2.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"),
+            "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_h2.hip"), os.path.join(_CSRC, "lm_engine_h3.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"),
             os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), os.path.join(_CSRC, "lm_gnn_ppo.hip"), os.path.join(_CSRC, "lm_optim.hip"), "-o", out]
 
 
@@ -453,8 +453,9 @@ class Engine:
     @property
     def step_variant(self) -> str:
         """The velocity-drive kernel step() launches on this engine: "w1" (k_step, one wavefront per 16 envs), "w2" (k_step_w2, two such workgroups
-        per SIMD) or "h2" (k_step_h2, a helper wavefront per workgroup); DESIGN.md 5.1.  Every other kernel family reports "w1"."""
-        return ("w1", "w2", "h2")[self.lib.lm_internal_step_variant(self._h)]
+        per SIMD), "h2" (k_step_h2, a helper wavefront per workgroup) or "h3" (k_step_h3, two helper wavefronts per workgroup); DESIGN.md 5.1.
+        Every other kernel family reports "w1"."""
+        return ("w1", "w2", "h2", "h3")[self.lib.lm_internal_step_variant(self._h)]
 
     # ------------------------------------------------------------------
     def _check(self, rc: int):
