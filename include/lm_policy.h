@@ -118,6 +118,66 @@ int lm_rollout_set_episode_record(lm_rollout* r, float* record, int episode_cap)
  * after each lm_step. */
 int lm_episode_update(struct lm_engine* h, const float* rewards, const int64_t* dones, float* record, int episode_cap, void* stream);
 
+/* ---- trajectory record: what K chosen envs did, one row per control step (what the reference's co-training task does with RECORD_JOINT = True,
+ * tasks/joint_train_locomanipulation/joint_locomanipulation.py:36-46, 556-563, 861-874: it appends the 12 driven joint positions of one env
+ * after every control step until that env's reset flag is raised, then np.save()s them).  Like the episode record it is a switch of a plan,
+ * off after lm_rollout_create; a plan or engine that does not use it launches the kernels and writes the bits it did before it existed.
+ *
+ * Two caller-owned device buffers, which persist across runs (episodes cross rollout boundaries) and which the caller zeroes to start a
+ * measurement; K = 1 .. LM_TRAJ_MAX_ENVS tracked env ids, distinct, in [0, N):
+ *   rows   float [K][max_rows][LM_TRAJ_COLS]   slot-major: one slot's trajectory is a contiguous slice; a row is 256 B; 16-byte aligned
+ *   header int32 [K][4]                        per slot { rows written, episodes completed, rows dropped, 0 }
+ * After step t, a row of slot k tracking env e is a column-by-column COPY of what stands in the engine's state (the SoA rows R_* of
+ * csrc/lm_dynamics.h, lm_ptr LM_PTR_STATE), in its counters (LM_PTR_CNT) and in the step's outputs after that step - no arithmetic, so every
+ * path writes the same bits:
+ *   columns  0-11  q (R_Q), in the order robot.joint_positions exposes: the order of the reference's recordings
+ *           12-23  qd (R_QD)
+ *           24-30  free body position and quaternion (w, x, y, z): R_FB0 + 0..6, the base, for an env of a locomotion block; R_FB1 + 0..6, the
+ *                  plate, for an env of a manipulation block (a co-training engine: chosen per env by split_env)
+ *           31-42  R_LACT: the clamped actions the step applied
+ *           43-54  R_LTIP (below)
+ *           55-58  R_GOAL: the goal quaternion (w, x, y, z)
+ *           59     rewards[t][e]
+ *           60     dones[t][e] != 0, as 0.0 / 1.0
+ *           61     goal_reset_buf (LM_PTR_CNT row 2) != 0, as 0.0 / 1.0
+ *           62     progress_buf (row 4) as float
+ *           63     episode_count (row 5) as float
+ * R_LTIP after a step holds the four foot-tip positions (limb-major x, y, z) of the POST-step state in the frame of the robot's base body -
+ * the moving base for a locomotion env, the fixed inverted base for a manipulation env: the task layer's `btip`, which it keeps as the
+ * next step's last_tip.  They are NOT world positions (lm_forward_kinematics gives those); for an env reset by this step they are the tips
+ * of the reset pose after its first control step.
+ * An env flagged done still shows its TERMINAL state in that row: the reset happens at the start of the next lm_step.
+ *
+ * Update rule, per slot after each step (hdr = the slot's header, cap = episode_cap, <= 0: no cap):
+ *   if (cap > 0 && hdr.episodes >= cap) skip;
+ *   if (hdr.rows < max_rows) { write row hdr.rows; hdr.rows += 1; } else hdr.dropped += 1;      never a store past the slot
+ *   if (done) hdr.episodes += 1;
+ * With cap = 1, a record zeroed when every env is about to reset (lm_reset_all) is exactly the reference's recording: one row per control
+ * step from the reset step up to and including the terminal step.
+ *
+ * lm_rollout_set_trajectory_record validates on the host - LM_EINVAL for a null plan, K outside [1, LM_TRAJ_MAX_ENVS], an id outside [0, N)
+ * or repeated, null rows / header, max_rows < 1, rows not 16-byte aligned, a calling thread whose current device is not the engine's - and
+ * copies the ids into device memory owned by the plan (-2 if that allocation or copy fails).  It is SYNCHRONOUS (a blocking host-to-device copy, as the randomisation setters of
+ * lm_engine.h): do not call it while a run of the plan is in flight.  env_ids_host == NULL or K == 0 switches recording off.  Flipping it
+ * invalidates a captured graph as lm_rollout_set_episode_record does (re-captured on the next run, never refused).
+ * Enqueue and graph runs update the record after every lm_step (after lm_episode_update when both are attached); enqueue, graph and
+ * persistent runs fill identical buffers and identical records.  The persistent kernels that keep a trajectory record are builds of their
+ * own, shipped - the rule of the episode record - only where they compile with 0 bytes of scratch memory: the MLP on 64-wide observations,
+ * alone and together with deterministic mode and / or an episode record.  For the MLP on 88-wide observations and for the GNN,
+ * LM_ROLLOUT_PERSISTENT returns -1 for a plan with a trajectory record attached and LM_ROLLOUT_AUTO takes the graph; randomised engines and
+ * engines with contact reporting on keep their rule (graph / enqueue only). */
+#define LM_TRAJ_COLS 64
+#define LM_TRAJ_MAX_ENVS 256
+int lm_rollout_set_trajectory_record(lm_rollout* r, const int32_t* env_ids_host, int K, float* rows, int32_t* header, int max_rows,
+                                     int episode_cap);
+
+/* The same update as one small launch (one wavefront per slot, lane = column), for callers that step with lm_step themselves: env_ids_dev
+ * device int32 [K]; rewards [N] and dones int64 [N] as lm_step wrote them for the step that has just been enqueued on `stream`.  An id
+ * outside [0, N) is skipped by the kernel, not read through.  Any engine family: PD, randomised, contact reporting, co-training.
+ * Returns 0, LM_EINVAL (a null argument, K outside [1, LM_TRAJ_MAX_ENVS], max_rows < 1, misaligned rows, the wrong device) or -2. */
+int lm_trajectory_update(struct lm_engine* h, const int32_t* env_ids_dev, int K, const float* rewards, const int64_t* dones, float* rows,
+                         int32_t* header, int max_rows, int episode_cap, void* stream);
+
 /* ---- PPO update (csrc/lm_ppo.hip): the loss and parameter gradient of one mini-batch of train/ppo.py PPO.update for the MLP policy above,
  * and GAE.  The optimiser, the gradient-norm clip, the KL-adaptive rate and the scalers stay with the caller.
  *

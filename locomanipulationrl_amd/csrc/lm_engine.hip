@@ -41,6 +41,7 @@ extern "C" void lm_dbg_pass2_read(unsigned int* out, int clear) {
 #include "lm_policy_dev.h"
 #include "lm_internal.h"
 #include "lm_step.h"      // the device code of the step: lm_samplers.h, lm_dynamics.h, lm_task.h, lm_step.h
+#include "lm_traj_dev.h"         // RolloutTraj, LM_EV_TRAJ: the persistent builds with a trajectory record (lm_engine_tr.hip)
 #include "lm_rollout_dev.h"      // RolloutDev, step_dispatch, PolicySmem: shared with the evaluation builds (lm_engine_ev.hip)
 
 // The step kernels.  One launch per step(); a wavefront picks its specialisation (task mode x actuator family) from the kernel arguments.  The
@@ -993,7 +994,13 @@ int lm_internal_rollout(lm_engine* h, int policy, const LmRolloutArgs& R, hipStr
   D.rewards = R.rewards; D.dones = R.dones; D.acc_steps = R.acc_steps; D.T = R.T; D.noise_seed = R.noise_seed;
   static const bool streaming = getenv("LM_ROLLOUT_STREAMING_MLP") != nullptr;      // kernel experiments: the four-wavefront tile with streamed weights
   const int ev = (R.deterministic ? LM_EV_DET : 0) | (R.record ? LM_EV_REC : 0);
-  if (ev) {      // evaluation builds (lm_engine_ev.hip; the MLP always on the resident tile)
+  if (R.traj_K) {      // builds that keep a trajectory record (lm_engine_tr.hip)
+    if (!lm_internal_rollout_trajectories(policy, R.nobs, R.deterministic, R.record != nullptr)) return fail(-1, "persistent rollout: no build keeps a trajectory record for this policy / observation width / switches; such plans run through the graph mode");
+    RolloutEv E; E.record = R.record; E.cap = R.episode_cap;
+    RolloutTraj TJ; TJ.ids = R.traj_ids; TJ.rows = R.traj_rows; TJ.header = R.traj_header; TJ.K = R.traj_K; TJ.max_rows = R.traj_max_rows; TJ.cap = R.traj_cap;
+    if (lm_internal_launch_rollout_tr(&A, &D, &E, &TJ, ev | LM_EV_TRAJ, policy, R.nobs, h->nblocks, s)) return -1;
+  }
+  else if (ev) {      // evaluation builds (lm_engine_ev.hip; the MLP always on the resident tile)
     if (R.record && !lm_internal_rollout_records(policy, R.nobs)) return fail(-1, "persistent rollout: no recording build for this policy / observation width; recording plans run through the graph mode");
     RolloutEv E; E.record = R.record; E.cap = R.episode_cap;
     if (lm_internal_launch_rollout_ev(&A, &D, &E, ev, policy, R.nobs, h->nblocks, s)) return -1;
@@ -1017,9 +1024,16 @@ int lm_internal_rollout_supported(const lm_engine* h, int policy, int nobs) {
 // observations.  (With the record, the 88-wide MLP build needs 116 - 156 bytes of scratch per lane against 60 - 72 without and the GNN build
 // 268 - 292 against 236 - 240: not shipped; those plans record in the graph mode.)
 int lm_internal_rollout_records(int policy, int nobs) { return policy == LM_POLICY_MLP && nobs == 64; }
+int lm_internal_rollout_trajectories(int policy, int nobs, int deterministic, int episode_record) {
+  return lm_internal_rollout_tr_built(LM_EV_TRAJ | (deterministic ? LM_EV_DET : 0) | (episode_record ? LM_EV_REC : 0), policy, nobs);
+}
 int lm_internal_on_device(const lm_engine* h) { return h && on_device(h); }
 void lm_internal_episode_info(const lm_engine* h, int* split, int* max_episode) {
   *split = h->split; max_episode[0] = h->h_params[0].max_episode; max_episode[1] = h->h_params[h->n_tasks == 2 ? 1 : 0].max_episode;
+}
+void lm_internal_trajectory_info(const lm_engine* h, int* split, int* free_body_row) {
+  *split = h->split;
+  for (int b = 0; b < 2; b++) free_body_row[b] = h->h_params[h->n_tasks == 2 ? b : 0].mode == LM_MODE_LOCO ? R_FB0 : R_FB1;
 }
 
 uint64_t lm_internal_args_key(const lm_engine* h) {

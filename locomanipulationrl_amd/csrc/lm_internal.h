@@ -13,6 +13,7 @@ struct LmRolloutArgs {
   int T, nobs; uint32_t noise_seed;
   int deterministic;           // lm_rollout_set_deterministic: the *_ev instantiations with the mean-action epilogue
   float* record; int episode_cap;      // lm_rollout_set_episode_record (record may be null: no recording)
+  const int32_t* traj_ids; int traj_K; float* traj_rows; int32_t* traj_header; int traj_max_rows, traj_cap;      // lm_rollout_set_trajectory_record (traj_K 0: off)
 };
 
 // T x (policy forward -> sampling -> step) + the bootstrap forward in ONE kernel launch (lm_engine.hip); policy = LM_POLICY_MLP / _GNN.
@@ -22,10 +23,16 @@ int lm_internal_rollout(lm_engine* h, int policy, const LmRolloutArgs& R, hipStr
 int lm_internal_rollout_supported(const lm_engine* h, int policy, int nobs);
 // 1 when the persistent kernel has a build that keeps the episode record for this policy / observation width (else recording plans take the graph)
 int lm_internal_rollout_records(int policy, int nobs);
+// its twin for the trajectory record: 1 when the persistent kernel has a build that keeps one for this policy / observation width together with these
+// other switches (deterministic actions, an episode record attached); else plans with a trajectory record take the graph
+int lm_internal_rollout_trajectories(int policy, int nobs, int deterministic, int episode_record);
 // 1 when the calling thread's current device is the engine's
 int lm_internal_on_device(const lm_engine* h);
 // what the episode record needs of the engine: first env of the second parameter block (N when there is one block) and max_episode of both
 void lm_internal_episode_info(const lm_engine* h, int* split, int* max_episode);
+// what the trajectory record needs of the engine: the same split, and per parameter block the state row its free body starts at (R_FB0, the
+// base, for a locomotion block; R_FB1, the plate, for a manipulation block)
+void lm_internal_trajectory_info(const lm_engine* h, int* split, int* free_body_row);
 // what a captured lm_step launch has baked into its kernel arguments and the engine may change afterwards: the goal / domain-randomisation seed
 // (lm_set_seed) and which of the unclipped views are kept current (lm_ptr).  A hipGraph captured under another key is re-captured.
 uint64_t lm_internal_args_key(const lm_engine* h);

@@ -23,6 +23,7 @@
 #include "lm_rng.h"
 #include "lm_policy_dev.h"
 #include "lm_internal.h"
+#include "lm_traj_dev.h"
 #include <new>
 
 #ifdef LM_GNN_STAMPS
@@ -81,6 +82,19 @@ __global__ void __launch_bounds__(256) k_episode_update(const float* __restrict_
   const int env = blockIdx.x * blockDim.x + threadIdx.x;
   if (env >= N) return;
   episode_update(record, (size_t)N, (size_t)env, rewards[env], dones[env] != 0, cnt[2 * (size_t)N + env] != 0, env >= split ? M1 : M0, cap);
+}
+
+// trajectory record of one step (include/lm_policy.h; lm_traj_dev.h): one wavefront per slot, lane = column.  For callers that step with
+// lm_step themselves and for the enqueue / graph rollouts.  An id outside [0, N) is skipped, not read through.
+__global__ void __launch_bounds__(64) k_trajectory_update(const float* __restrict__ state, const int64_t* __restrict__ cnt, const float* __restrict__ rewards,
+                                                          const int64_t* __restrict__ dones, const int32_t* __restrict__ env_ids, int K, int N, int split,
+                                                          int fb0, int fb1, float* __restrict__ rows, int32_t* __restrict__ header, int max_rows, int cap) {
+  const int k = blockIdx.x;
+  if (k >= K) return;
+  const int env = env_ids[k];
+  if (env < 0 || env >= N) return;
+  traj_update_slot(state, cnt, rewards, dones, N, env, env >= split ? fb1 : fb0, rows + (size_t)k * (size_t)max_rows * LM_TRAJ_COLS, header + 4 * (size_t)k,
+                   max_rows, cap, threadIdx.x);
 }
 
 extern "C" {
@@ -147,6 +161,8 @@ struct lm_rollout {
   uint64_t exec_env_key;                                          // engine seed + requested views baked into the captured kernel arguments
   bool det; float* record; int cap;                               // lm_rollout_set_deterministic / lm_rollout_set_episode_record
   bool exec_det; float* exec_record; int exec_cap;                // ... as they were when the graph was captured
+  int32_t* traj_ids; int traj_K; float* traj_rows; int32_t* traj_header; int traj_max_rows, traj_cap;      // lm_rollout_set_trajectory_record (traj_K 0: off);
+  uint64_t traj_gen, exec_traj_gen;                               //   traj_ids: device [LM_TRAJ_MAX_ENVS], the plan's own.  traj_gen counts the calls of the setter
 };
 
 static int rollout_enqueue(lm_rollout* r, hipStream_t s) {
@@ -167,6 +183,11 @@ static int rollout_enqueue(lm_rollout* r, hipStream_t s) {
                  r->extras ? r->extras + (size_t)t * LM_NUM_EXTRAS : nullptr, s);
     if (rc) return rc;
     if (r->record) { rc = lm_episode_update(r->env, r->rewards + (size_t)t * N, r->dones + (size_t)t * N, r->record, r->cap, s); if (rc) return rc; }
+    if (r->traj_K) {
+      rc = lm_trajectory_update(r->env, r->traj_ids, r->traj_K, r->rewards + (size_t)t * N, r->dones + (size_t)t * N, r->traj_rows, r->traj_header, r->traj_max_rows,
+                                r->traj_cap, s);
+      if (rc) return rc;
+    }
   }
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
@@ -191,6 +212,7 @@ int lm_rollout_create(lm_rollout** out, lm_engine* env, int policy, const float*
   r->params = policy_params; r->log_std = log_std; r->obs = obs; r->actions = actions; r->logp = logp; r->values = values;
   r->rewards = rewards; r->dones = dones; r->extras = extras; r->exec = nullptr; r->exec_stream = nullptr;
   r->det = false; r->record = nullptr; r->cap = 0;
+  r->traj_ids = nullptr; r->traj_K = 0; r->traj_rows = nullptr; r->traj_header = nullptr; r->traj_max_rows = 0; r->traj_cap = 0; r->traj_gen = 0; r->exec_traj_gen = 0;
   r->cnt = (const int64_t*)lm_ptr(env, LM_PTR_CNT);
   if (hipMalloc((void**)&r->mean_tmp, (size_t)r->N * 12 * sizeof(float)) != hipSuccess) { delete r; return lm_internal_fail(-2, "lm_rollout_create: hipMalloc failed"); }
   r->acc_steps = nullptr;
@@ -226,27 +248,67 @@ int lm_episode_update(lm_engine* h, const float* rewards, const int64_t* dones, 
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+int lm_rollout_set_trajectory_record(lm_rollout* r, const int32_t* env_ids_host, int K, float* rows, int32_t* header, int max_rows, int episode_cap) {
+  if (!r) return lm_internal_fail(-1, "lm_rollout_set_trajectory_record: null plan");
+  if (!lm_internal_on_device(r->env)) return lm_internal_fail(-1, "lm_rollout_set_trajectory_record: the calling thread's current device is not the engine's device");
+  if (!env_ids_host || K == 0) { r->traj_K = 0; r->traj_rows = nullptr; r->traj_header = nullptr; r->traj_gen++; return 0; }      // recording off
+  if (K < 1 || K > LM_TRAJ_MAX_ENVS) return lm_internal_fail(-1, "lm_rollout_set_trajectory_record: K must be in [1, LM_TRAJ_MAX_ENVS]");
+  if (!rows || !header) return lm_internal_fail(-1, "lm_rollout_set_trajectory_record: null rows or header");
+  if (max_rows < 1) return lm_internal_fail(-1, "lm_rollout_set_trajectory_record: max_rows must be at least 1");
+  if (reinterpret_cast<uintptr_t>(rows) & 15) return lm_internal_fail(-1, "lm_rollout_set_trajectory_record: rows must be 16-byte aligned");
+  {
+    int32_t sorted[LM_TRAJ_MAX_ENVS];      // distinct ids in [0, N): an insertion sort of at most 256 values
+    for (int k = 0; k < K; k++) {
+      const int32_t e = env_ids_host[k];
+      if (e < 0 || e >= r->N) return lm_internal_fail(-1, "lm_rollout_set_trajectory_record: an env id outside [0, N)");
+      int j = k;
+      while (j > 0 && sorted[j - 1] > e) { sorted[j] = sorted[j - 1]; j--; }
+      if (j > 0 && sorted[j - 1] == e) return lm_internal_fail(-1, "lm_rollout_set_trajectory_record: an env id is repeated");
+      sorted[j] = e;
+    }
+  }
+  if (!r->traj_ids && hipMalloc((void**)&r->traj_ids, LM_TRAJ_MAX_ENVS * sizeof(int32_t)) != hipSuccess) { r->traj_ids = nullptr; return lm_internal_fail(-2, "lm_rollout_set_trajectory_record: hipMalloc failed"); }
+  if (hipMemcpy(r->traj_ids, env_ids_host, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) return lm_internal_fail(-2, "lm_rollout_set_trajectory_record: hipMemcpy failed");
+  r->traj_K = K; r->traj_rows = rows; r->traj_header = header; r->traj_max_rows = max_rows; r->traj_cap = episode_cap > 0 ? episode_cap : 0; r->traj_gen++;
+  return 0;
+}
+
+int lm_trajectory_update(lm_engine* h, const int32_t* env_ids_dev, int K, const float* rewards, const int64_t* dones, float* rows, int32_t* header, int max_rows,
+                         int episode_cap, void* stream) {
+  if (!h || !env_ids_dev || !rewards || !dones || !rows || !header) return lm_internal_fail(-1, "lm_trajectory_update: null handle, env ids, rewards, dones, rows or header");
+  if (K < 1 || K > LM_TRAJ_MAX_ENVS) return lm_internal_fail(-1, "lm_trajectory_update: K must be in [1, LM_TRAJ_MAX_ENVS]");
+  if (max_rows < 1) return lm_internal_fail(-1, "lm_trajectory_update: max_rows must be at least 1");
+  if (reinterpret_cast<uintptr_t>(rows) & 15) return lm_internal_fail(-1, "lm_trajectory_update: rows must be 16-byte aligned");
+  if (!lm_internal_on_device(h)) return lm_internal_fail(-1, "lm_trajectory_update: the calling thread's current device is not the engine's device");
+  int split = 0, fb[2] = {0, 0}; lm_internal_trajectory_info(h, &split, fb);
+  hipLaunchKernelGGL(k_trajectory_update, dim3(K), dim3(64), 0, (hipStream_t)stream, (const float*)lm_ptr(h, LM_PTR_STATE), (const int64_t*)lm_ptr(h, LM_PTR_CNT), rewards,
+                     dones, env_ids_dev, K, lm_num_envs(h), split, fb[0], fb[1], rows, header, max_rows, episode_cap > 0 ? episode_cap : 0);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 int lm_rollout_run(lm_rollout* r, int use_graph, void* stream) {
   if (!r) return lm_internal_fail(-1, "lm_rollout_run: null plan");
   hipStream_t s = (hipStream_t)stream;
   if (use_graph == LM_ROLLOUT_AUTO)      // a persistent block holds a whole CU (512 registers per lane): one resident generation of blocks, or the graph
     use_graph = (r->persistent_ok && lm_internal_rollout_supported(r->env, r->policy, r->nobs) && (!r->record || lm_internal_rollout_records(r->policy, r->nobs)) &&
-                 (r->N + 15) / 16 <= r->n_cu) ? LM_ROLLOUT_PERSISTENT : LM_ROLLOUT_GRAPH;      // asked again: contact-force reporting may have been switched on since
+                 (!r->traj_K || lm_internal_rollout_trajectories(r->policy, r->nobs, r->det, r->record != nullptr)) && (r->N + 15) / 16 <= r->n_cu) ? LM_ROLLOUT_PERSISTENT : LM_ROLLOUT_GRAPH;      // asked again: contact-force reporting may have been switched on since
   if (!use_graph) return rollout_enqueue(r, s);
   if (use_graph == LM_ROLLOUT_PERSISTENT) {
     // the whole rollout in one kernel (un-randomised engines); same results as the other two modes
     LmRolloutArgs R; R.params = r->params; R.log_std = r->log_std; R.obs = r->obs; R.actions = r->actions; R.logp = r->logp; R.values = r->values;
     R.rewards = r->rewards; R.extras = r->extras; R.dones = r->dones; R.acc_steps = r->acc_steps; R.T = r->T; R.nobs = r->nobs; R.noise_seed = r->seed;
     R.deterministic = r->det ? 1 : 0; R.record = r->record; R.episode_cap = r->cap;
+    R.traj_ids = r->traj_ids; R.traj_K = r->traj_K; R.traj_rows = r->traj_rows; R.traj_header = r->traj_header; R.traj_max_rows = r->traj_max_rows; R.traj_cap = r->traj_cap;
     return lm_internal_rollout(r->env, r->policy, R, s);
   }
-  if (r->exec && (r->exec_env_key != lm_internal_args_key(r->env) || r->exec_det != r->det || r->exec_record != r->record || r->exec_cap != r->cap)) {
+  if (r->exec && (r->exec_env_key != lm_internal_args_key(r->env) || r->exec_det != r->det || r->exec_record != r->record || r->exec_cap != r->cap ||
+                  r->exec_traj_gen != r->traj_gen)) {
     // lm_set_seed / a first lm_ptr() for a view / lm_enable_contact_forces / a switch of the plan flipped since the capture: the graph's kernels or their arguments are stale
     (void)hipGraphExecDestroy(r->exec); r->exec = nullptr;
   }
   if (!r->exec) {
     // capture the 4T+1 launches once; every pointer in them is fixed for the lifetime of the plan
-    r->exec_env_key = lm_internal_args_key(r->env); r->exec_det = r->det; r->exec_record = r->record; r->exec_cap = r->cap;
+    r->exec_env_key = lm_internal_args_key(r->env); r->exec_det = r->det; r->exec_record = r->record; r->exec_cap = r->cap; r->exec_traj_gen = r->traj_gen;
     hipGraph_t g = nullptr;
     hipStream_t cs = s;
     bool own = false;
@@ -268,6 +330,7 @@ int lm_rollout_destroy(lm_rollout* r) {
   if (r->exec) (void)hipGraphExecDestroy(r->exec);
   if (r->mean_tmp) (void)hipFree(r->mean_tmp);
   if (r->acc_steps) (void)hipFree(r->acc_steps);
+  if (r->traj_ids) (void)hipFree(r->traj_ids);
   delete r;
   return 0;
 }

@@ -25,6 +25,7 @@ CONTACT_ROWS = 16        # LM_CONTACT_ROWS
 EPISODE_ROWS = 9         # LM_EPISODE_ROWS (include/lm_policy.h)
 # rows of the episode record
 EPISODE = dict(running_return=0, running_length=1, episodes=2, sum_return=3, sum_length=4, goal=5, timeout=6, failure=7, last_return=8)
+TRAJ_COLS, TRAJ_MAX_ENVS = 64, 256      # LM_TRAJ_COLS, LM_TRAJ_MAX_ENVS (include/lm_policy.h)
 PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS, PTR_CONTACT, PTR_DR_ACTUATOR = range(14)
 
 # names of the exported C symbols (checked by tests/test_abi.py against include/lm_engine.h)
@@ -33,6 +34,7 @@ EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass
            "lm_gnn_param_count", "lm_gnn_forward", "lm_mlp_param_count", "lm_mlp_forward", "lm_mlp_param_count_obs", "lm_mlp_forward_obs",
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy",
            "lm_rollout_set_deterministic", "lm_rollout_set_episode_record", "lm_episode_update",
+           "lm_rollout_set_trajectory_record", "lm_trajectory_update",
            "lm_mlp_grad_param_count", "lm_mlp_ppo_grad", "lm_mlp_ppo_grad_workspace", "lm_mlp_ppo_grad_geometry", "lm_gae",
            "lm_gnn_grad_param_count", "lm_gnn_ppo_grad", "lm_gnn_ppo_grad_workspace", "lm_gnn_ppo_grad_geometry",
            "lm_optim_state_len", "lm_optim_state_init", "lm_adam_clip_step", "lm_kl_adaptive_lr"]
@@ -207,7 +209,7 @@ def hipcc_command(extra, out):
     # -amdgpu-mfma-vgpr-form: the MFMA accumulators of the policy tiles live in ordinary VGPRs, so the VALU work on them (ELU, max aggregation,
     # LDS stores) needs no v_accvgpr_read per element (504 of them in k_gnn_forward)
     return [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
-            "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_h2.hip"), os.path.join(_CSRC, "lm_engine_h3.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"),
+            "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_h2.hip"), os.path.join(_CSRC, "lm_engine_h3.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"), os.path.join(_CSRC, "lm_engine_tr.hip"),
             os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), os.path.join(_CSRC, "lm_gnn_ppo.hip"), os.path.join(_CSRC, "lm_optim.hip"), "-o", out]
 
 
@@ -268,6 +270,8 @@ def load_library() -> C.CDLL:
     lib.lm_rollout_set_deterministic.argtypes = [vp, ip]
     lib.lm_rollout_set_episode_record.argtypes = [vp, fp, ip]
     lib.lm_episode_update.argtypes = [vp, fp, vp, fp, ip, vp]
+    lib.lm_rollout_set_trajectory_record.argtypes = [vp, vp, ip, fp, vp, ip, ip]
+    lib.lm_trajectory_update.argtypes = [vp, vp, ip, fp, vp, fp, vp, ip, ip, vp]
     lib.lm_mlp_grad_param_count.argtypes = [ip]
     lib.lm_mlp_ppo_grad.argtypes = [fp, fp, fp, fp, fp, fp, fp, ip, ip, C.POINTER(LmPpoHyper), fp, fp, vp, C.c_longlong, vp]
     lib.lm_mlp_ppo_grad_workspace.argtypes = [ip, ip]; lib.lm_mlp_ppo_grad_workspace.restype = C.c_longlong
@@ -598,10 +602,12 @@ class Rollout:
 
     Evaluation switches (both off by default; a plan that uses neither runs the kernels it always ran): `deterministic` makes actions[t] the
     forward's mean and logp[t] the density at the mean; `episode_record` (an EpisodeRecord or a float (9, N) device tensor) is updated after
-    every step, for the first `episode_cap` episodes of each env when the cap is positive."""
+    every step, for the first `episode_cap` episodes of each env when the cap is positive; `trajectory_record` (a TrajectoryRecord) gets one
+    row per step of its tracked envs, in every mode ("persistent" on the MLP with 64-wide observations; elsewhere it refuses such a plan and
+    "auto" takes the graph)."""
 
     def __init__(self, engine: Engine, policy: int, packed_params, log_std, T: int, noise_seed: int = 0, deterministic: bool = False,
-                 episode_record=None, episode_cap: int = 0):
+                 episode_record=None, episode_cap: int = 0, trajectory_record=None):
         torch = engine.torch
         self.engine, self.T, self.N = engine, int(T), engine.num_envs
         assert engine.num_obs == 64 or (engine.num_obs == 88 and policy == POLICY_MLP), "the GNN reads the 64-wide layout; the MLP 64 or 88"
@@ -621,11 +627,13 @@ class Rollout:
                                           p(self.obs), p(self.actions), p(self.logp), p(self.values), p(self.rewards), p(self.dones), p(self.extras))
         if rc != 0:
             raise EngineError(f"lm_rollout_create failed ({rc})")
-        self.deterministic, self.episode_record, self.episode_cap = False, None, 0
+        self.deterministic, self.episode_record, self.episode_cap, self.trajectory_record = False, None, 0, None
         if deterministic:
             self.set_deterministic(True)
         if episode_record is not None:
             self.set_episode_record(episode_record, episode_cap)
+        if trajectory_record is not None:
+            self.set_trajectory_record(trajectory_record)
 
     def _set(self, rc):
         if rc != 0:
@@ -645,6 +653,20 @@ class Rollout:
         with self.engine.torch.cuda.device(self.engine.device):
             self._set(self.engine.lib.lm_rollout_set_episode_record(self._h, Engine._p(t), int(episode_cap)))
         self.episode_record, self.episode_cap = record, int(episode_cap)
+
+    def set_trajectory_record(self, record=None):
+        """Attach a TrajectoryRecord of this plan's engine (None: recording off) from the next run on; the plan keeps it alive.  Synchronous:
+        the env ids are copied to the device before the call returns."""
+        lib = self.engine.lib
+        with self.engine.torch.cuda.device(self.engine.device):
+            if record is None:
+                self._set(lib.lm_rollout_set_trajectory_record(self._h, None, 0, None, None, 0, 0))
+            else:
+                assert record.engine is self.engine, "the record tracks envs of another engine"
+                ids = (C.c_int32 * record.K)(*record.env_ids)
+                self._set(lib.lm_rollout_set_trajectory_record(self._h, ids, record.K, Engine._p(record.rows), Engine._p(record.header), record.max_rows,
+                                                               record.episode_cap))
+        self.trajectory_record = record
 
     MODES = {"enqueue": 0, "graph": 1, "persistent": 2, "auto": 3}
 
@@ -743,3 +765,107 @@ class EpisodeRecord:
         if split:
             out["loco"] = self._reduce(rec[:, :split]); out["mani"] = self._reduce(rec[:, split:])
         return out
+
+
+class TrajectoryRecord:
+    """The trajectory record of include/lm_policy.h: one row of 64 floats per control step for each of K tracked envs - q, qd, the free body's
+    pose (base or plate), the applied actions, the foot tips in the base frame, the goal, reward, done and the counters (COLUMNS) - a copy
+    of what stands in the engine after the step.  Owns rows (K, max_rows, 64) float32, header (K, 4) int32 {rows written, episodes completed,
+    rows dropped, 0} and the id tensor, on the engine's device.  Hand it to a Rollout (trajectory_record=) or call update() after every
+    engine step; zero() starts a measurement (zero it when every env is about to reset and episode_cap = 1 records what the reference's
+    RECORD_JOINT does).  On an engine without the C library (CPU tensors: the oracle backend of the tests) update() applies the same rule
+    in torch."""
+
+    COLUMNS = dict(q=slice(0, 12), qd=slice(12, 24), free_body=slice(24, 31), last_actions=slice(31, 43), last_tip=slice(43, 55), goal=slice(55, 59),
+                   reward=slice(59, 60), done=slice(60, 61), goal_reset=slice(61, 62), progress=slice(62, 63), episode_count=slice(63, 64))
+
+    def __init__(self, engine, env_ids, max_rows: int, episode_cap: int = 1):
+        import torch
+        self.torch, self.engine, self.N = torch, engine, int(engine.num_envs)
+        ids = [int(e) for e in env_ids]
+        if not 1 <= len(ids) <= TRAJ_MAX_ENVS:
+            raise ValueError(f"a trajectory record tracks 1 .. {TRAJ_MAX_ENVS} envs, not {len(ids)}")
+        if len(set(ids)) != len(ids):
+            raise ValueError("a trajectory record's env ids must be distinct")
+        if min(ids) < 0 or max(ids) >= self.N:
+            raise ValueError(f"env ids must lie in [0, {self.N})")
+        if int(max_rows) < 1:
+            raise ValueError("max_rows must be at least 1")
+        self.env_ids, self.K, self.max_rows, self.episode_cap = ids, len(ids), int(max_rows), max(int(episode_cap), 0)
+        dev = engine.cnt.device
+        self.rows = torch.zeros((self.K, self.max_rows, TRAJ_COLS), dtype=torch.float32, device=dev)
+        self.header = torch.zeros((self.K, 4), dtype=torch.int32, device=dev)
+        self.ids = torch.tensor(ids, dtype=torch.int32, device=dev)
+        self._native = hasattr(engine, "lib") and hasattr(engine, "_h")
+        if not self._native:          # a backend with the engine's interface and its parameter blocks on the host: the column -> state row map in torch
+            params = list(engine.params)
+            split = int(engine.split) if len(params) == 2 else self.N
+            src = torch.empty((self.K, 59), dtype=torch.int64)
+            for k, e in enumerate(ids):
+                fb = ROW["base_pos"] if int(params[1 if e >= split else 0].mode) == 0 else ROW["plate_pos"]
+                src[k] = torch.tensor([ROW["q"] + c for c in range(12)] + [ROW["qd"] + c for c in range(12)] + [fb + c for c in range(7)] +
+                                      [ROW["last_actions"] + c for c in range(12)] + [ROW["last_tip"] + c for c in range(12)] + [ROW["goal"] + c for c in range(4)])
+            self._src = src.to(dev)
+
+    def zero(self):
+        self.rows.zero_(); self.header.zero_()
+
+    def update(self, rew, resets):
+        """One step: rew (N,) float32 and resets (N,) int64 as step() returned them; everything else is read from the engine."""
+        e, torch = self.engine, self.torch
+        if self._native:
+            rew = e._f32(rew, (self.N,))
+            assert resets.dtype == torch.int64 and resets.is_contiguous() and resets.device == e.device and tuple(resets.shape) == (self.N,)
+            with torch.cuda.device(e.device):
+                e._check(e.lib.lm_trajectory_update(e._h, Engine._p(self.ids), self.K, Engine._p(rew), Engine._p(resets), Engine._p(self.rows), Engine._p(self.header),
+                                                    self.max_rows, self.episode_cap, e._stream()))
+            return
+        ids = self.ids.long()
+        state, cnt = e.state.to(self.rows.device), e.cnt.to(self.rows.device)
+        row = torch.empty((self.K, TRAJ_COLS), dtype=torch.float32, device=self.rows.device)
+        row[:, :59] = state[self._src, ids[:, None]]
+        done = resets.to(self.rows.device)[ids] != 0
+        row[:, 59] = rew.to(self.rows.device, torch.float32)[ids]; row[:, 60] = done.float(); row[:, 61] = (cnt[2, ids] != 0).float()
+        row[:, 62] = cnt[4, ids].float(); row[:, 63] = cnt[5, ids].float()
+        H = self.header
+        live = torch.ones(self.K, dtype=torch.bool, device=H.device) if self.episode_cap <= 0 else H[:, 1] < self.episode_cap
+        room = live & (H[:, 0] < self.max_rows)
+        k = torch.nonzero(room).reshape(-1)
+        self.rows[k, H[k, 0].long()] = row[k]
+        H[:, 0] += room.int(); H[:, 2] += (live & ~room).int(); H[:, 1] += (live & done).int()
+
+    def episodes(self, slot: int):
+        """The rows of one slot cut at the done flags: a list of dicts of named numpy arrays (COLUMNS; single columns as (L,) vectors) with
+        "complete" (the episode's terminal row was recorded) and "truncated" (rows of this slot were dropped: the last episode is cut short)."""
+        hdr = self.header[slot].cpu().numpy()
+        rows = self.rows[slot, :int(hdr[0])].cpu().numpy()
+        ends = np.nonzero(rows[:, 60] != 0)[0].tolist()
+        cuts = [0] + [i + 1 for i in ends]
+        if cuts[-1] < len(rows):
+            cuts.append(len(rows))
+        out = []
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            ep = {name: (rows[a:b, sl] if sl.stop - sl.start > 1 else rows[a:b, sl.start]) for name, sl in self.COLUMNS.items()}
+            ep["complete"] = bool(rows[b - 1, 60] != 0)
+            ep["truncated"] = bool(hdr[2] > 0) and b == len(rows)
+            out.append(ep)
+        return out
+
+    def save_npy(self, directory: str, prefix: str = "trajectory"):
+        """Per tracked env e: <prefix>_env<e>.npy - the first recorded episode's q as float32 (L, 12), the format of the reference's recordings -
+        and <prefix>_env<e>.npz - every named column of every recorded episode (<name>_<episode index>) plus the slot's header.  Returns the
+        .npy paths."""
+        os.makedirs(directory, exist_ok=True)
+        paths = []
+        for slot, e in enumerate(self.env_ids):
+            eps = self.episodes(slot)
+            base = os.path.join(directory, f"{prefix}_env{e}")
+            q = eps[0]["q"] if eps else np.zeros((0, 12), dtype=np.float32)
+            np.save(base + ".npy", np.ascontiguousarray(q, dtype=np.float32))
+            arrays = {"header": self.header[slot].cpu().numpy(), "env": np.int32(e), "episodes": np.int32(len(eps))}
+            for i, ep in enumerate(eps):
+                for name in self.COLUMNS:
+                    arrays[f"{name}_{i}"] = ep[name]
+            np.savez(base + ".npz", **arrays)
+            paths.append(base + ".npy")
+        return paths

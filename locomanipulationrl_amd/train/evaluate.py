@@ -13,7 +13,7 @@ from typing import Dict, Optional
 
 import torch
 
-from ..lib import EpisodeRecord
+from ..lib import EpisodeRecord, TrajectoryRecord
 
 ROLLOUT_STEPS = 48      # the reference's rollout length (scripts/skrl_ppo_locomotion.py:87)
 
@@ -25,11 +25,14 @@ def _scaler_moments(obs_scaler):
 
 
 def evaluate(env, model, obs_scaler=None, episodes_per_env: int = 1, max_steps: Optional[int] = None, deterministic: bool = True,
-             fused: bool = True, noise_seed: int = 2000, return_record: bool = False) -> Dict:
+             fused: bool = True, noise_seed: int = 2000, return_record: bool = False, record_envs=None, record_rows: Optional[int] = None) -> Dict:
     """Run `model` on `env` until every env has completed `episodes_per_env` episodes (the FIRST ones of every env: no bias towards short
     episodes) or `max_steps` env steps have been taken (default: episodes_per_env x the longest max_episode + one rollout).  Returns
     EpisodeRecord.summary() plus "steps", "envs_short" (envs that completed fewer episodes than asked for) and "deterministic"; with
-    `return_record` also the (9, N) record itself (a host tensor) under "record"."""
+    `return_record` also the (9, N) record itself (a host tensor) under "record".
+    `record_envs` (a list of env ids) attaches a TrajectoryRecord for those envs with the same episode cap and room for `record_rows` rows per
+    env (default: the task's longest max_episode x episodes_per_env); it is zeroed together with the episode record, at the reset, and
+    returned under "trajectory"."""
     task = env._task
     engine = task.engine
     cap = int(episodes_per_env)
@@ -37,11 +40,17 @@ def evaluate(env, model, obs_scaler=None, episodes_per_env: int = 1, max_steps: 
     if max_steps is None:
         max_steps = cap * max(int(p.max_episode) for p in task.engine_params()) + ROLLOUT_STEPS
     record = EpisodeRecord(engine)
+    traj = None
+    if record_envs is not None:
+        rows = int(record_rows) if record_rows is not None else cap * max(int(p.max_episode) for p in task.engine_params())
+        traj = TrajectoryRecord(engine, record_envs, rows, episode_cap=cap)
     # env.reset() by hand, so that the record sees the reset step too: an episode's length counts it (progress_buf is 1 after it), and the
     # timeout / failure split compares the recorded length with max_episode
     task.reset()
     o, rew, resets, _ = env.step(torch.zeros((env.num_envs, task.num_actions), device=task.rl_device))
     record.update(rew.contiguous(), resets.contiguous(), cap)
+    if traj is not None:
+        traj.update(rew.contiguous(), resets.contiguous())
     obs = o["obs"]
     mean_, var_, eps, clip = _scaler_moments(obs_scaler)
     on_gpu = record.record.is_cuda
@@ -55,7 +64,7 @@ def evaluate(env, model, obs_scaler=None, episodes_per_env: int = 1, max_steps: 
         model.refresh(engine.device, mean_, var_, eps, clip)
         packed = model._packed.clone(); log_std = model.log_std_parameter.detach().clone().float().contiguous()
         ro = task.make_rollout(kind, packed, log_std, ROLLOUT_STEPS, noise_seed=noise_seed, deterministic=deterministic,
-                               episode_record=record, episode_cap=cap)
+                               episode_record=record, episode_cap=cap, trajectory_record=traj)
         ro.obs[0].copy_(obs)
         while steps < max_steps and not done():
             ro.run("auto")
@@ -77,6 +86,8 @@ def evaluate(env, model, obs_scaler=None, episodes_per_env: int = 1, max_steps: 
                 act = mean if deterministic else mean + log_std.exp() * torch.randn_like(mean)
                 o, rew, resets, _ = env.step(act)
                 record.update(rew.contiguous(), resets.contiguous(), cap)
+                if traj is not None:
+                    traj.update(rew.contiguous(), resets.contiguous())
                 obs = o["obs"]; steps += 1
     out = record.summary()
     out["steps"] = steps
@@ -84,4 +95,6 @@ def evaluate(env, model, obs_scaler=None, episodes_per_env: int = 1, max_steps: 
     out["deterministic"] = bool(deterministic)
     if return_record:
         out["record"] = record.record.detach().cpu().clone()
+    if traj is not None:
+        out["trajectory"] = traj
     return out

@@ -2,7 +2,9 @@
 """Evaluate a checkpoint written by tools/train_ppo.py --save: mean actions (the reference's eval = True / agent.set_mode('eval')),
 the first --episodes-per-env episodes of every env, one JSON line with the summary (episodes, mean_return, mean_length, success_rate,
 timeout_rate, failure_rate, ...; co-training tasks also per half).
-    python tools/eval_policy.py --checkpoint agent.pt --task QuadrupedPoseControl [--num-envs 4096 --episodes-per-env 1 --stochastic --randomize]"""
+    python tools/eval_policy.py --checkpoint agent.pt --task QuadrupedPoseControl [--num-envs 4096 --episodes-per-env 1 --stochastic --randomize]
+--record-envs 0,2048 --record-dir DIR also writes, per listed env, DIR/<task>_env<e>.npy (the first episode's joint positions, float32 (L, 12):
+the format of the reference's RECORD_JOINT files) and DIR/<task>_env<e>.npz (every column of the trajectory record), and names them in the JSON line."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -19,7 +21,13 @@ def main():
     ap.add_argument("--stochastic", action="store_true", help="sample actions as in training instead of taking the mean")
     ap.add_argument("--randomize", action="store_true", help="switch the task YAML's domain_randomization block on")
     ap.add_argument("--no-fused", action="store_true", help="step from Python instead of the fused rollout")
+    ap.add_argument("--record-envs", default=None, help="comma-separated env ids whose trajectories are recorded")
+    ap.add_argument("--record-dir", default=None, help="where the recorded trajectories are written (needs --record-envs)")
+    ap.add_argument("--record-rows", type=int, default=None, help="rows kept per recorded env (default: max_episode x episodes per env)")
     a = ap.parse_args()
+    record_envs = [int(x) for x in a.record_envs.split(",")] if a.record_envs else None
+    if (record_envs is None) != (a.record_dir is None):
+        raise SystemExit("--record-envs and --record-dir go together")
     sd = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     torch.manual_seed(a.seed)
     env = lm.make_env(a.task, num_envs=a.num_envs, seed=a.seed,
@@ -35,7 +43,12 @@ def main():
         model = SharedMLP(num_observations=n_obs)
     model.load_state_dict(sd["model"]); model = model.to("cuda:0")
     scaler = RunningStandardScaler(n_obs, "cuda:0"); scaler.load_state_dict(sd["obs_scaler"])
-    out = evaluate(env, model, scaler, episodes_per_env=a.episodes_per_env, max_steps=a.max_steps, deterministic=not a.stochastic, fused=not a.no_fused)
+    out = evaluate(env, model, scaler, episodes_per_env=a.episodes_per_env, max_steps=a.max_steps, deterministic=not a.stochastic, fused=not a.no_fused,
+                   record_envs=record_envs, record_rows=a.record_rows)
+    traj = out.pop("trajectory", None)
+    if traj is not None:
+        out["trajectory_files"] = traj.save_npy(a.record_dir, a.task)
+        out["trajectory_header"] = traj.header.cpu().tolist()
     print(json.dumps({"task": a.task, "num_envs": a.num_envs, "checkpoint": a.checkpoint, **out}), flush=True)
     env.close()
 
