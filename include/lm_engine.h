@@ -155,6 +155,24 @@ typedef struct lm_actuator_dr { lm_dr_channel ch[LM_DR_ACTUATOR_CHANNELS]; } lm_
  * is a derived output of the last launch, not state: nothing reads it back, and a checkpoint (Engine.state_dict) does not carry it. */
 #define LM_CONTACT_ROWS 16
 
+/* Per-env physics parameters held by the caller, opt-in per engine with lm_enable_env_params.  The hold table is
+ * float [LM_ENV_PARAM_ROWS][N]: the three records one after the other,
+ *   rows [0, 43)    as LM_PTR_DR_PHYS      max efforts 12, max joint velocities 12, gravity 3, base force 3, joint damping 12, mu_env 1
+ *   rows [43, 66)   as LM_PTR_DR_MASS      plate mass, plate inertia factor, 21 body masses (table order)
+ *   rows [66, 69)   as LM_PTR_DR_ACTUATOR  kp, kd, command latency in sub-steps
+ * with a row mask beside it (lm_env_params_held).  A row is held for ALL envs of the engine or for none, so the switches of the step stay uniform
+ * over a wavefront.  In every lm_step of such an engine the value of a held row replaces what the row's channel produced (or the nominal value,
+ * with the channel off), after the channels have drawn and before the records are written: the records report the held values.  A held value is
+ * used exactly as stored - no floor (lm_set_env_params validated it), no re-derivation: the held plate mass is the mass whatever the inertia
+ * factor, and a held mu row IS mu_env, the coefficient the contact solve uses, after friction_scale and the combine mode.  What the drawing path
+ * derives is derived the same way: kp / kd from whichever of the two are held or drawn; the body-mass and plate paths of the sub-step go on when
+ * one of their rows is held, as they do when their channel is on.  On a co-training engine the plate rows act on the manipulation block only.
+ * Not combined yet (follow-ups): contact-force reporting (each of lm_enable_env_params / lm_enable_contact_forces(h, 1) is refused while the
+ * other is on) and the staged entry points, which refuse every randomised engine. */
+#define LM_ENV_PARAM_ROWS (LM_DR_PHYS_ROWS + LM_DR_MASS_ROWS + LM_DR_ACTUATOR_ROWS)   /* 69 */
+#define LM_ENV_PARAM_MASS_ROW0 LM_DR_PHYS_ROWS                          /* 43 */
+#define LM_ENV_PARAM_ACTUATOR_ROW0 (LM_DR_PHYS_ROWS + LM_DR_MASS_ROWS)  /* 66 */
+
 typedef struct lm_params {
   int32_t abi_version;     /* LM_ABI_VERSION of the header the caller was compiled against */
   int32_t params_size;     /* the caller's sizeof(lm_params) */
@@ -238,8 +256,10 @@ typedef enum {
   LM_PTR_CONTACT = 12,  /* float [LM_CONTACT_ROWS][N]  per-foot contact forces and contact fractions of the last reporting launch; NULL until
                            lm_enable_contact_forces(h, 1).  One more row of N floats follows it, all bits set, which no kernel writes (a guard
                            the tests read) */
-  LM_PTR_DR_ACTUATOR = 13 /* float [LM_DR_ACTUATOR_ROWS][N]  kp, kd and the command latency d (sub-steps) the last step used; the nominal values
+  LM_PTR_DR_ACTUATOR = 13,/* float [LM_DR_ACTUATOR_ROWS][N]  kp, kd and the command latency d (sub-steps) the last step used; the nominal values
                            (pd_kp, kd, 0) until an actuator channel draws; randomised engines only (NULL otherwise) */
+  LM_PTR_ENV_PARAMS = 14  /* float [LM_ENV_PARAM_ROWS][N]  the hold table of lm_enable_env_params (NULL until then).  Read it freely; write it
+                           through lm_set_env_params, which validates and sets the mask */
 } lm_ptr_kind;
 
 /* Create an engine for n_envs environments on the current HIP device.
@@ -291,9 +311,33 @@ int lm_set_actuator_randomization(lm_engine* h, int block, const lm_actuator_dr*
  * picks the graph, LM_ROLLOUT_ENQUEUE and LM_ROLLOUT_GRAPH leave the LAST step's record in the buffer.  A rollout plan created before the
  * switch stays valid: its graph is re-captured on the next run, as after lm_set_seed, so the switch is never refused on account of a plan.
  * A hipGraph the CALLER captured around lm_step keeps the kernel of capture time.
- * LM_EINVAL: null handle, or the calling thread's current device is not the engine's.  Synchronous (allocation, blocking clear): not to be
- * called while a graph that contains lm_step is being captured. */
+ * LM_EINVAL: null handle, the calling thread's current device is not the engine's, or on != 0 on an engine with env params enabled
+ * (lm_enable_env_params; combining the two is a follow-up).  Synchronous (allocation, blocking clear): not to be called while a graph that
+ * contains lm_step is being captured. */
 int lm_enable_contact_forces(lm_engine* h, int on);
+
+/* Per-env parameters held by the caller (see LM_ENV_PARAM_ROWS).  lm_enable_env_params allocates the hold table and its mask with nothing
+ * held; from then on lm_step launches builds of the randomised kernels that apply the holds (k_step_dr_hp, k_step_dr_pd_hp: one launch, as
+ * before); an engine that never enables launches exactly the kernels it launched before this entry point existed.  There is no way back.
+ * Rollouts (lm_policy.h): LM_ROLLOUT_AUTO / GRAPH / ENQUEUE work (LM_ROLLOUT_PERSISTENT refuses every randomised engine); a plan created before
+ * the call stays valid: its graph is re-captured on the next run.  Holding, changing or clearing rows afterwards needs no re-capture: table
+ * and mask live in device memory.  A hipGraph the CALLER captured around lm_step keeps the kernel of capture time.
+ * LM_EINVAL: null handle; the calling thread's current device is not the engine's; an engine created without dr_enabled (the un-randomised
+ * kernels carry no per-env parameters: create the engine with dr_enabled and no channel on); contact-force reporting on.  Synchronous
+ * (allocation, blocking clear), like lm_enable_contact_forces. */
+int lm_enable_env_params(lm_engine* h);
+/* Hold rows [row0, row0 + nrows) at values_host, a HOST float [nrows][N].  Everything is validated on the host before anything is copied;
+ * a refused call leaves table and mask as they were.  LM_EINVAL: null argument; not enabled; foreign device; rows outside the table; a value
+ * that is not finite; a mass, the plate's inertia factor, kp or kd that is not > 0; mu, a max effort, a max joint velocity or a joint damping
+ * that is < 0; a latency that is not whole or outside [0, substeps] of a block that reads it; a row that no block of the engine reads: kp
+ * without a position gain (variant 0 in velocity or effort drive), kd in effort drive, latency on variant 0, the plate rows on an engine
+ * without a manipulation block.  The copy is blocking. */
+int lm_set_env_params(lm_engine* h, int row0, int nrows, const float* values_host);
+/* Rows [row0, row0 + nrows) follow their channel - or the nominal value - again from the next step on.  A mass / actuator record row that no
+ * channel writes shows the nominal value again.  Blocking. */
+int lm_clear_env_params(lm_engine* h, int row0, int nrows);
+/* mask_out[0] bit r: row r (< 64) is held; mask_out[1] bit r - 64: row r.  LM_EINVAL: null argument, or not enabled. */
+int lm_env_params_held(const lm_engine* h, uint64_t* mask_out);
 
 /* One VecEnvRLGames.step(): reset flagged envs, clamp + apply actions, controlFrequencyInv physics
  * sub-steps, observations / reward / termination.  (vec_env_rlgames.py:56-79)

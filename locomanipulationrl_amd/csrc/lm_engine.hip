@@ -533,6 +533,10 @@ struct lm_engine {
   bool view_obs, view_states, view_terms;      // lm_ptr() handed out obs_buf / states_buf / the reward terms: lm_step keeps them current from then on
   float* d_contact;        // [LM_CONTACT_ROWS][N] contact record, allocated by the first lm_enable_contact_forces(h, 1) (LM_PTR_CONTACT)
   bool contact_on;         // lm_step / lm_substeps launch the *_cf kernels and write d_contact
+  float* d_env_params;     // [LM_ENV_PARAM_ROWS][N] hold table followed by the row mask uint64 [2] (at env_mask_offset), allocated by lm_enable_env_params (LM_PTR_ENV_PARAMS);
+                           // while it exists lm_step launches k_step_dr_hp / k_step_dr_pd_hp
+  uint64_t env_mask[2];    // host copy of the row mask
+  unsigned char mass_ch_on[2][LM_DR_MASS_CHANNELS], actuator_ch_on[2][LM_DR_ACTUATOR_CHANNELS];      // which mass / actuator channels the setters switched on, per block
   char* d_stats;           // int64 {num_successes, num_resets} x {all, first task, second task}; float success_rate x 3 at byte 48;
                            // uint32 count of contained blow-ups at byte 60
   lm_params h_params[2];
@@ -727,11 +731,14 @@ int lm_create(lm_engine** out, int n_envs, const float* table, const lm_params* 
 
 int lm_destroy(lm_engine* h) {
   if (!h) return LM_OK;
-  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_reset_dr, h->d_mass_dr, h->d_actuator_dr, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats, h->d_contact};
+  void* ptrs[] = {h->d_params, h->d_table, h->d_state, h->d_cnt, h->d_drc, h->d_dr_phys, h->d_reset_dr, h->d_mass_dr, h->d_actuator_dr, h->d_obs, h->d_states, h->d_rew, h->d_extras, h->d_terms, h->d_acc, h->d_stats, h->d_contact, h->d_env_params};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   delete h;
   return LM_OK;
 }
+
+// the row mask of the hold table sits behind its LM_ENV_PARAM_ROWS x N floats, at the next 8-byte boundary (N may be odd)
+static size_t env_mask_offset(int N) { return ((size_t)LM_ENV_PARAM_ROWS * (size_t)N + 1) & ~(size_t)1; }
 
 static StepArgs make_args(lm_engine* h, const float* actions, const float* goal_rand, float* out_obs, float* out_states, float* out_rew, int64_t* out_resets) {
   StepArgs A;
@@ -740,7 +747,8 @@ static StepArgs make_args(lm_engine* h, const float* actions, const float* goal_
   A.W.stats = (char*)h->d_stats; A.W.extras = h->d_extras; A.W.out_extras = nullptr; A.W.split_block = h->split / ENVS_PER_WAVE; A.W.acc_rows = h->acc_rows;
   A.W.out_obs = out_obs; A.W.out_states = out_states; A.W.out_rew = out_rew; A.W.out_resets = out_resets;
   A.N = h->N; A.split = h->split; A.seed = h->seed; A.skip_reset = 0; A.nsub = -1; A.drc = h->d_drc; A.dr_phys = h->d_dr_phys; A.reset_dr = h->d_reset_dr; A.mass_dr = h->d_mass_dr;
-  A.reserved = nullptr; A.contact = h->contact_on ? h->d_contact : nullptr; A.reserved2 = nullptr; A.actuator_dr = h->d_actuator_dr;
+  A.env_params = h->d_env_params; A.contact = h->contact_on ? h->d_contact : nullptr; A.actuator_dr = h->d_actuator_dr;
+  A.env_mask = h->d_env_params ? (const uint64_t*)(h->d_env_params + env_mask_offset(h->N)) : nullptr;
   for (int t = 0; t < 2; t++) A.kind[t] = h->h_params[t].variant * 2 + (h->h_params[t].mode == LM_MODE_MANI ? 1 : 0);
   return A;
 }
@@ -785,6 +793,7 @@ int lm_step(lm_engine* h, const float* actions, const float* goal_rand, float* o
   if (variant == 1) lm_internal_launch_step_w2(&A, h->nblocks, s);      // locomotion, two wavefronts per SIMD: ahead beyond 32 768 envs
   else if (variant == 3) lm_internal_launch_step_h3(&A, h->nblocks, s);      // two helper wavefronts per workgroup: ahead up to one workgroup per CU
   else if (variant == 2) lm_internal_launch_step_h2(&A, h->nblocks, s);      // a helper wavefront per workgroup: ahead while half the SIMDs are idle
+  else if (h->d_env_params) lm_internal_launch_step_hp(&A, pd ? 1 : 0, h->nblocks, s);      // caller-held per-env parameters: the randomised kernels with the hold (never with reporting)
   else {
     void (*kern)(StepArgs) = h->contact_on ? (h->dr_enabled ? (pd ? k_step_dr_pd_cf : k_step_dr_cf) : (pd ? k_step_pd_cf : k_step_cf))      // with reporting: one-wavefront kernels at every size
                                            : (h->dr_enabled ? (pd ? k_step_dr_pd : k_step_dr) : (pd ? k_step_pd : k_step));
@@ -856,6 +865,7 @@ int lm_set_mass_randomization(lm_engine* h, int block, const lm_mass_dr* md) {
     }
   }
   HIPCHK(hipMemcpy(h->d_mass_dr + block, md, sizeof(lm_mass_dr), hipMemcpyHostToDevice));
+  for (int c = 0; c < LM_DR_MASS_CHANNELS; c++) h->mass_ch_on[block][c] = md->ch[c].enabled != 0;
   return LM_OK;
 }
 
@@ -880,12 +890,14 @@ int lm_set_actuator_randomization(lm_engine* h, int block, const lm_actuator_dr*
       return fail_fn(LM_EINVAL, fn, "the distribution's range reaches a non-positive gain");
   }
   HIPCHK(hipMemcpy(h->d_actuator_dr + block, ad, sizeof(lm_actuator_dr), hipMemcpyHostToDevice));
+  for (int c = 0; c < LM_DR_ACTUATOR_CHANNELS; c++) h->actuator_ch_on[block][c] = ad->ch[c].enabled != 0;
   return LM_OK;
 }
 
 int lm_enable_contact_forces(lm_engine* h, int on) {
   if (!h) return fail(LM_EINVAL, "lm_enable_contact_forces: null handle");
   CHECK_DEVICE(h, "lm_enable_contact_forces");
+  if (on && h->d_env_params) return fail(LM_EINVAL, "lm_enable_contact_forces: the engine holds per-env parameters (lm_enable_env_params); the two do not combine yet");
   if (on && !h->d_contact) {
     const size_t row = (size_t)h->N * sizeof(float), bytes = LM_CONTACT_ROWS * row;
     float* p = nullptr;
@@ -894,6 +906,120 @@ int lm_enable_contact_forces(lm_engine* h, int on) {
     h->d_contact = p;
   }
   h->contact_on = on != 0;
+  return LM_OK;
+}
+
+// ---- per-env parameters held by the caller (include/lm_engine.h, LM_ENV_PARAM_ROWS)
+enum { HP_MASS0 = LM_DR_PHYS_ROWS, HP_ACT0 = LM_DR_PHYS_ROWS + LM_DR_MASS_ROWS };      // first rows of the mass and the actuator part
+static int env_params_entry(const char* fn, const lm_engine* h, int row0, int nrows) {
+  if (!h) return fail_fn(LM_EINVAL, fn, "null handle");
+  if (!on_device(h)) return fail_fn(LM_EINVAL, fn, "the calling thread's current device is not the engine's device");
+  if (!h->d_env_params) return fail_fn(LM_EINVAL, fn, "env params are not enabled on this engine (lm_enable_env_params)");
+  if (row0 < 0 || nrows <= 0 || row0 > LM_ENV_PARAM_ROWS - nrows) return fail_fn(LM_EINVAL, fn, "rows outside [0, LM_ENV_PARAM_ROWS)");
+  return LM_OK;
+}
+static int env_mask_upload(lm_engine* h) {
+  HIPCHK(hipMemcpy(h->d_env_params + env_mask_offset(h->N), h->env_mask, sizeof(h->env_mask), hipMemcpyHostToDevice));
+  return LM_OK;
+}
+// NULL when some block of the engine reads row r, or why none does (the reasons of lm_set_actuator_randomization / lm_set_mass_randomization)
+static const char* env_row_refusal(const lm_engine* h, int r) {
+  bool mani = false, kp = false, kd = false, pdv = false;
+  for (int b = 0; b < h->n_tasks; b++) {
+    const lm_params& P = h->h_params[b];
+    mani |= P.mode == LM_MODE_MANI; pdv |= P.variant != 0;
+    kp |= P.variant != 0 || P.drive_mode == LM_DRIVE_POSITION; kd |= P.variant != 0 || P.drive_mode != LM_DRIVE_EFFORT;
+  }
+  if ((r == HP_MASS0 || r == HP_MASS0 + 1) && !mani) return "the plate rows exist on engines with a manipulation block only";
+  if (r == HP_ACT0 + LM_DR_ACTUATOR_KP && !kp) return "the kp row needs a position gain (variants 1 / 2, or variant 0 in position drive mode)";
+  if (r == HP_ACT0 + LM_DR_ACTUATOR_KD && !kd) return "the kd row has nothing to act on in effort drive mode (gains off)";
+  if (r == HP_ACT0 + LM_DR_ACTUATOR_LATENCY && !pdv) return "the latency row exists on the PD-actuator variants (1 / 2) only";
+  return nullptr;
+}
+// NULL when `v` may be held in row r for env e, or what is wrong with it
+static const char* env_value_refusal(const lm_engine* h, int r, size_t e, float v) {
+  if (!std::isfinite(v)) return "non-finite value";
+  if (r >= HP_MASS0 && r < HP_ACT0 + LM_DR_ACTUATOR_LATENCY) return v > 0.f ? nullptr : "masses, the plate's inertia factor, kp and kd must be positive";
+  if (r == HP_ACT0 + LM_DR_ACTUATOR_LATENCY) {
+    const lm_params& P = h->h_params[(int)e >= h->split ? 1 : 0];
+    if (v != floorf(v) || v < 0.f || (P.variant != 0 && v > (float)P.substeps)) return "the latency must be a whole number of sub-steps in [0, substeps]";
+    return nullptr;
+  }
+  if (r >= 24 && r < 30) return nullptr;      // gravity and the base-link force: any finite vector
+  return v >= 0.f ? nullptr : "mu, max efforts, max joint velocities and joint damping must not be negative";
+}
+// mass / actuator row r: is it written by a channel of block b, and its nominal value there (what the record shows until a channel draws)
+static bool env_row_has_channel(const lm_engine* h, int r, int b) {
+  if (r == HP_MASS0) return h->mass_ch_on[b][LM_DR_MASS_PLATE] || h->mass_ch_on[b][LM_DR_MASS_PLATE_DENSITY];
+  if (r == HP_MASS0 + 1) return h->mass_ch_on[b][LM_DR_MASS_PLATE] || h->mass_ch_on[b][LM_DR_MASS_PLATE_DENSITY];
+  if (r < HP_ACT0) return h->mass_ch_on[b][LM_DR_MASS_BODIES];
+  if (r < HP_ACT0 + LM_DR_ACTUATOR_LATENCY) return h->actuator_ch_on[b][LM_DR_ACTUATOR_KP] || h->actuator_ch_on[b][LM_DR_ACTUATOR_KD];
+  return h->actuator_ch_on[b][LM_DR_ACTUATOR_LATENCY];
+}
+static float env_row_nominal(const lm_engine* h, int r, int b) {
+  const lm_params& P = h->h_params[b];
+  if (r == HP_MASS0) return P.plate_mass;
+  if (r == HP_MASS0 + 1) return 1.f;
+  if (r < HP_ACT0) return h->h_body_mass[r - HP_MASS0 - 2];
+  return r == HP_ACT0 ? P.pd_kp : r == HP_ACT0 + 1 ? P.kd : 0.f;
+}
+
+int lm_enable_env_params(lm_engine* h) {
+  const char* const fn = "lm_enable_env_params";
+  if (!h) return fail_fn(LM_EINVAL, fn, "null handle");
+  if (!on_device(h)) return fail_fn(LM_EINVAL, fn, "the calling thread's current device is not the engine's device");
+  if (!h->dr_enabled) return fail_fn(LM_EINVAL, fn, "the engine was created without dr_enabled (the un-randomised kernels carry no per-env parameters)");
+  if (h->contact_on) return fail_fn(LM_EINVAL, fn, "contact-force reporting is on (lm_enable_contact_forces); the two do not combine yet");
+  if (h->d_env_params) return LM_OK;
+  const size_t bytes = env_mask_offset(h->N) * sizeof(float) + sizeof(h->env_mask);
+  float* p = nullptr;
+  HIPCHK(hipMalloc((void**)&p, bytes));
+  if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(p); return fail(LM_EHIP, "lm_enable_env_params: clearing the table failed"); }
+  h->env_mask[0] = h->env_mask[1] = 0; h->d_env_params = p;
+  return LM_OK;
+}
+
+int lm_set_env_params(lm_engine* h, int row0, int nrows, const float* values_host) {
+  const char* const fn = "lm_set_env_params";
+  if (int rc = env_params_entry(fn, h, row0, nrows)) return rc;
+  if (!values_host) return fail_fn(LM_EINVAL, fn, "null values");
+  const size_t N = (size_t)h->N;
+  for (int r = row0; r < row0 + nrows; r++) {      // everything is checked before anything is copied
+    if (const char* why = env_row_refusal(h, r)) return fail_fn(LM_EINVAL, fn, why);
+    const float* row = values_host + (size_t)(r - row0) * N;
+    for (size_t e = 0; e < N; e++)
+      if (const char* why = env_value_refusal(h, r, e, row[e])) return fail_fn(LM_EINVAL, fn, why);
+  }
+  HIPCHK(hipMemcpy(h->d_env_params + (size_t)row0 * N, values_host, (size_t)nrows * N * sizeof(float), hipMemcpyHostToDevice));
+  for (int r = row0; r < row0 + nrows; r++) h->env_mask[r >> 6] |= 1ull << (r & 63);
+  return env_mask_upload(h);
+}
+
+int lm_clear_env_params(lm_engine* h, int row0, int nrows) {
+  const char* const fn = "lm_clear_env_params";
+  if (int rc = env_params_entry(fn, h, row0, nrows)) return rc;
+  const size_t N = (size_t)h->N;
+  for (int r = row0; r < row0 + nrows; r++) {
+    if (!((h->env_mask[r >> 6] >> (r & 63)) & 1ull)) continue;
+    h->env_mask[r >> 6] &= ~(1ull << (r & 63));
+    if (r < HP_MASS0) continue;      // LM_PTR_DR_PHYS is rewritten by every step
+    // a mass / actuator record row is written only while a channel or a hold of its group is on: where no channel writes it, it shows the nominal value again
+    float* rec = r < HP_ACT0 ? (float*)(h->d_mass_dr + 2) + (size_t)(r - HP_MASS0) * N : (float*)(h->d_actuator_dr + 2) + (size_t)(r - HP_ACT0) * N;
+    float* tmp = new (std::nothrow) float[N];
+    if (!tmp) return fail(LM_ENOMEM, "lm_clear_env_params: host allocation failed");
+    hipError_t err = hipMemcpy(tmp, rec, N * sizeof(float), hipMemcpyDeviceToHost);
+    for (size_t e = 0; e < N && err == hipSuccess; e++) { const int b = (int)e >= h->split ? 1 : 0; if (!env_row_has_channel(h, r, b)) tmp[e] = env_row_nominal(h, r, b); }
+    if (err == hipSuccess) err = hipMemcpy(rec, tmp, N * sizeof(float), hipMemcpyHostToDevice);
+    delete[] tmp;
+    if (err != hipSuccess) return fail(LM_EHIP, "lm_clear_env_params: restoring a record row failed");
+  }
+  return env_mask_upload(h);
+}
+
+int lm_env_params_held(const lm_engine* h, uint64_t* mask_out) {
+  if (!h || !mask_out) return fail(LM_EINVAL, "lm_env_params_held: null argument");
+  if (!h->d_env_params) return fail(LM_EINVAL, "lm_env_params_held: env params are not enabled on this engine (lm_enable_env_params)");
+  mask_out[0] = h->env_mask[0]; mask_out[1] = h->env_mask[1];
   return LM_OK;
 }
 
@@ -972,6 +1098,7 @@ void* lm_ptr(lm_engine* h, int kind) {
     case LM_PTR_STATS: return h->d_stats;
     case LM_PTR_TERMS: h->view_terms = true; return h->d_terms;
     case LM_PTR_CONTACT: return h->d_contact;
+    case LM_PTR_ENV_PARAMS: return h->d_env_params;
     default: return nullptr;
   }
 }
@@ -1037,6 +1164,6 @@ void lm_internal_trajectory_info(const lm_engine* h, int* split, int* free_body_
 }
 
 uint64_t lm_internal_args_key(const lm_engine* h) {
-  return h ? ((uint64_t)h->seed | ((uint64_t)((h->view_obs ? 1 : 0) | (h->view_states ? 2 : 0) | (h->view_terms ? 4 : 0) | (h->contact_on ? 8 : 0)) << 32)) : 0ull;
+  return h ? ((uint64_t)h->seed | ((uint64_t)((h->view_obs ? 1 : 0) | (h->view_states ? 2 : 0) | (h->view_terms ? 4 : 0) | (h->contact_on ? 8 : 0) | (h->d_env_params ? 16 : 0)) << 32)) : 0ull;
 }
 int lm_internal_fail(int code, const char* msg) { return fail(code, msg); }

@@ -34,7 +34,8 @@ void lm_internal_episode_info(const lm_engine* h, int* split, int* max_episode);
 // base, for a locomotion block; R_FB1, the plate, for a manipulation block)
 void lm_internal_trajectory_info(const lm_engine* h, int* split, int* free_body_row);
 // what a captured lm_step launch has baked into its kernel arguments and the engine may change afterwards: the goal / domain-randomisation seed
-// (lm_set_seed) and which of the unclipped views are kept current (lm_ptr).  A hipGraph captured under another key is re-captured.
+// (lm_set_seed), which of the unclipped views are kept current (lm_ptr), and which kernels lm_step launches (lm_enable_contact_forces,
+// lm_enable_env_params).  A hipGraph captured under another key is re-captured.
 uint64_t lm_internal_args_key(const lm_engine* h);
 // records a message for lm_last_error() (thread-local, lm_engine.hip) and returns `code`
 int lm_internal_fail(int code, const char* msg);

@@ -303,7 +303,7 @@ int lm_rollout_run(lm_rollout* r, int use_graph, void* stream) {
   }
   if (r->exec && (r->exec_env_key != lm_internal_args_key(r->env) || r->exec_det != r->det || r->exec_record != r->record || r->exec_cap != r->cap ||
                   r->exec_traj_gen != r->traj_gen)) {
-    // lm_set_seed / a first lm_ptr() for a view / lm_enable_contact_forces / a switch of the plan flipped since the capture: the graph's kernels or their arguments are stale
+    // lm_set_seed / a first lm_ptr() for a view / lm_enable_contact_forces / lm_enable_env_params / a switch of the plan flipped since the capture: the graph's kernels or their arguments are stale
     (void)hipGraphExecDestroy(r->exec); r->exec = nullptr;
   }
   if (!r->exec) {

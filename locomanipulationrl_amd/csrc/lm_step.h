@@ -38,22 +38,26 @@ struct StepArgs {
                                     // reset to (k_step_dr / k_step_dr_pd only; kept last so that no other member moves)
   const lm_mass_dr* mass_dr;        // mass channels of the two blocks, followed by float [LM_DR_MASS_ROWS][N]: the masses the last step used
                                     // (k_step_dr / k_step_dr_pd only; appended for the same reason)
-  void* reserved;                   // unused: with it the arguments that follow StepArgs (k_substeps, k_fk, k_rollout ...) keep their 16-byte phase, so those kernels' code stays as it was
+  const float* env_params;          // [LM_ENV_PARAM_ROWS][N] per-env parameters held by the caller (k_step_dr_hp / k_step_dr_pd_hp only; NULL unless lm_enable_env_params).  In the
+                                    // slot that used to be reserved: the arguments that follow StepArgs (k_substeps, k_fk, k_rollout ...) keep their 16-byte phase
   float* contact;                   // [LM_CONTACT_ROWS][N] contact record (the *_cf kernels only; NULL unless reporting is on; appended for the same reason)
-  void* reserved2;                  // unused: keeps the 16-byte phase of what follows StepArgs, as `reserved` does
+  const uint64_t* env_mask;         // [2] which rows of env_params are held (bit r of the 128: row r; the same kernels; the second formerly reserved slot)
   const lm_actuator_dr* actuator_dr;      // actuator channels of the two blocks, followed by float [LM_DR_ACTUATOR_ROWS][N]: kp, kd and latency the last
                                     // step used (the randomised kernels only; the new last member)
 };
 extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_w2(const StepArgs* A, int nblocks, hipStream_t s);      // k_step_w2's launcher (lm_engine_w2.hip), called by lm_step
 extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_h2(const StepArgs* A, int nblocks, hipStream_t s);      // k_step_h2's launcher (lm_engine_h2.hip), called by lm_step
 extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_h3(const StepArgs* A, int nblocks, hipStream_t s);      // k_step_h3's launcher (lm_engine_h3.hip), called by lm_step
+extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_hp(const StepArgs* A, int pd, int nblocks, hipStream_t s);      // k_step_dr_hp / k_step_dr_pd_hp's launcher (lm_engine_hp.hip), called by lm_step
 
 // REG0: substep()'s first drive pass runs on registers (1, the step kernels) or reads the stash back like the second (0: k_step_w2 and the
 // persistent rollouts, whose register budget has no room for it; same arithmetic, same bits)
 // HW: wavefront 0 of k_step_h2, whose helper wavefront computes the limb bias terms of every sub-step (helper_wave, lm_dynamics.h)
 // (HW 2: wavefront 0 of k_step_h3, whose second helper computes the contact terms too: helper_wave_terms.)  OW: that helper also streams the
 // staged obs / states of a full wavefront out (write_outputs, helper_write_outputs)
-template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0, int REG0 = 1, int HW = 0, int OW = 0>
+// HP: the randomised step of an engine with caller-held per-env parameters (lm_enable_env_params; k_step_dr_hp / k_step_dr_pd_hp, DR = 1 only): the
+// value of every held row of A.env_params replaces what the channels produced, before the record rows are written.  The mask is wave-uniform
+template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0, int REG0 = 1, int HW = 0, int OW = 0, int HP = 0>
 LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float* sTab, float* sObs, float* sSt, float4* sStash) {
   TableRegs TR; table_fetch(A.table, threadIdx.x, TR);
   const int lane = threadIdx.x, limb = lane & 3, envl = lane >> 2;
@@ -77,6 +81,10 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
     act[a] = A.actions[(size_t)env * 12 + jj[a]];
   }
   DrPhys X; uint32_t dr_step = 0; int64_t dr_rand_buf = 0, dr_reset_key = 0; bool reset_draw = false;
+  // HP: the row mask (bits 0..63, 64..68) and the table; held(r) may be lane-dependent through r, the mask itself is not
+  const uint64_t hp_lo = HP ? A.env_mask[0] : 0ull; const uint32_t hp_hi = HP ? (uint32_t)A.env_mask[1] : 0u; const float* hp = A.env_params;
+  const auto held = [&](int r) -> bool { return HP && (r < 64 ? (hp_lo >> r) & 1ull : (uint64_t)(hp_hi >> (r - 64)) & 1ull) != 0; };
+  const auto held_value = [&](int r, float x) -> float { return held(r) ? hp[(size_t)r * N + env] : x; };
   if (DR) {
     // ---- action noise on the raw actions (vec_env_rlgames.py:56-58; randomize.py:237-259): correlated noise keyed by the episode this
     // step belongs to (redrawn exactly when the reset flag is set), uncorrelated noise every frequency_interval calls
@@ -106,6 +114,13 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
       X.vmax[c] = dr_attr(P->dr[LM_DR_MAX_VELOCITY], A.seed, LM_DR_MAX_VELOCITY, env, dr_step, (uint32_t)dr_reset_key, jj[c], 0, P->max_joint_vel);
       X.cj[c] = dr_attr(P->dr[LM_DR_JOINT_DAMPING], A.seed, LM_DR_JOINT_DAMPING, env, dr_step, (uint32_t)dr_reset_key, jj[c], 0, P->joint_damping);
     }
+    if (HP) {      // rows of LM_PTR_DR_PHYS: max efforts 0, max joint velocities 12, gravity 24, base force 27, joint damping 30
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+        X.tmax[c] = held_value(jj[c], X.tmax[c]); X.vmax[c] = held_value(12 + jj[c], X.vmax[c]); X.cj[c] = held_value(30 + jj[c], X.cj[c]);
+        gv[c] = held_value(24 + c, gv[c]); fv[c] = held_value(27 + c, fv[c]);
+      }
+    }
     X.g = v3(gv[0], gv[1], gv[2]); X.f = v3(fv[0], fv[1], fv[2]);
     // contact material: mu_env = friction_scale x combine(feet, ground / plate); the block's mu when neither channel is on
     const lm_dr_channel& mr = P->dr_mat[LM_DR_MAT_ROBOT]; const lm_dr_channel& mo = P->dr_mat[LM_DR_MAT_OTHER];
@@ -115,6 +130,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
       const float fo = dr_material(mo, P->dr_mat_buckets[LM_DR_MAT_OTHER], A.seed, LM_DR_STREAM_MAT + LM_DR_MAT_OTHER, env, dr_step, (uint32_t)dr_reset_key, P->mat_mu_other);
       X.mu = fmaxf(P->friction_scale * friction_combine(P->friction_combine, fr, fo), 0.f);
     }
+    if (HP) X.mu = held_value(LM_DR_PHYS_MU, X.mu);      // mu_env itself: after friction_scale and the combine mode
     // mass channels: this lane's five limb bodies, the hub and, in a manipulation block, the plate.  The switches are
     // wave-uniform (one parameter block per wavefront): with all channels off nothing below runs and the sub-steps take the table's path
     {
@@ -122,6 +138,10 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
       const lm_dr_channel& cb = MD->ch[LM_DR_MASS_BODIES];
       X.mb_on = cb.enabled;
       X.mp_on = (MODE == 1 && (MD->ch[LM_DR_MASS_PLATE].enabled || MD->ch[LM_DR_MASS_PLATE_DENSITY].enabled)) ? 1 : 0;
+      if (HP) {      // rows LM_DR_PHYS_ROWS + (plate mass 0, plate inertia factor 1, body masses 2..22): a held row switches its path on, as its channel does
+        if ((hp_lo >> (LM_DR_PHYS_ROWS + 2)) != 0ull || (hp_hi & 3u) != 0u) X.mb_on = 1;
+        if (MODE == 1 && ((hp_lo >> LM_DR_PHYS_ROWS) & 3ull) != 0ull) X.mp_on = 1;
+      }
       float* mrec = (float*)(A.mass_dr + 2);
       if (X.mb_on) {
         const float* tn = A.table + HUB_FLOATS + limb * LIMB_STRIDE;      // nominal masses: the device table in memory (LDS is not filled yet)
@@ -130,8 +150,13 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
 #pragma unroll
         for (int j = 0; j < 5; j++)
           mm[j] = dr_mass(cb, A.seed, LM_DR_STREAM_MASS + LM_DR_MASS_BODIES, env, dr_step, (uint32_t)dr_reset_key, (uint32_t)(c0 + j), MD->body_p0[c0 + j], MD->body_p1[c0 + j], nom[j]);
+        if (HP) {
+#pragma unroll
+          for (int j = 0; j < 5; j++) mm[j] = held_value(LM_DR_PHYS_ROWS + 2 + c0 + j, mm[j]);
+        }
         X.m_s = mm[0]; X.m_41 = mk2(mm[1], mm[3]); X.m_32 = mk2(mm[2], mm[4]);
         X.m_hub = dr_mass(cb, A.seed, LM_DR_STREAM_MASS + LM_DR_MASS_BODIES, env, dr_step, (uint32_t)dr_reset_key, 0U, MD->body_p0[0], MD->body_p1[0], A.table[0]);
+        if (HP) X.m_hub = held_value(LM_DR_PHYS_ROWS + 2, X.m_hub);
         if (active) {
 #pragma unroll
           for (int j = 0; j < 5; j++) mrec[(size_t)(2 + c0 + j) * N + env] = mm[j];
@@ -142,6 +167,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
         const lm_dr_channel& cm = MD->ch[LM_DR_MASS_PLATE]; const lm_dr_channel& cd = MD->ch[LM_DR_MASS_PLATE_DENSITY];
         X.s_plate = dr_mass(cd, A.seed, LM_DR_STREAM_MASS + LM_DR_MASS_PLATE_DENSITY, env, dr_step, (uint32_t)dr_reset_key, 0U, cd.p0[0], cd.p1[0], 1.0f);
         X.m_plate = dr_mass(cm, A.seed, LM_DR_STREAM_MASS + LM_DR_MASS_PLATE, env, dr_step, (uint32_t)dr_reset_key, 0U, cm.p0[0], cm.p1[0], X.s_plate * P->plate_mass);
+        if (HP) { X.s_plate = held_value(LM_DR_PHYS_ROWS + 1, X.s_plate); X.m_plate = held_value(LM_DR_PHYS_ROWS, X.m_plate); }      // each as stored: a held factor does not re-derive the mass
         if (active && limb == 0) { mrec[env] = X.m_plate; mrec[(size_t)N + env] = X.s_plate; }
       }
     }
@@ -152,14 +178,18 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
       const lm_dr_channel& ckp = AD->ch[LM_DR_ACTUATOR_KP]; const lm_dr_channel& ckd = AD->ch[LM_DR_ACTUATOR_KD]; const lm_dr_channel& cl = AD->ch[LM_DR_ACTUATOR_LATENCY];
       float* arec = (float*)(A.actuator_dr + 2);
       X.kd = P->kd; X.gk = P->pd_kp / P->kd; X.lat_on = (VAR >= 1 && cl.enabled) ? 1 : 0; X.lat = 0;
-      if (ckp.enabled || ckd.enabled) {
-        const float kpe = dr_mass(ckp, A.seed, LM_DR_STREAM_ACTUATOR + LM_DR_ACTUATOR_KP, env, dr_step, (uint32_t)dr_reset_key, 0U, ckp.p0[0], ckp.p1[0], P->pd_kp);
+      constexpr int R_ACT = LM_DR_PHYS_ROWS + LM_DR_MASS_ROWS;      // HP: rows of kp, kd, latency
+      if (ckp.enabled || ckd.enabled || held(R_ACT) || held(R_ACT + 1)) {
+        float kpe = dr_mass(ckp, A.seed, LM_DR_STREAM_ACTUATOR + LM_DR_ACTUATOR_KP, env, dr_step, (uint32_t)dr_reset_key, 0U, ckp.p0[0], ckp.p1[0], P->pd_kp);
         X.kd = dr_mass(ckd, A.seed, LM_DR_STREAM_ACTUATOR + LM_DR_ACTUATOR_KD, env, dr_step, (uint32_t)dr_reset_key, 0U, ckd.p0[0], ckd.p1[0], P->kd);
+        if (HP) { kpe = held_value(R_ACT, kpe); X.kd = held_value(R_ACT + 1, X.kd); }
         X.gk = kpe / X.kd;
         if (active && limb == 0) { arec[env] = kpe; arec[(size_t)N + env] = X.kd; }
       }
+      if (HP && VAR >= 1 && held(R_ACT + 2)) X.lat_on = 1;
       if (VAR >= 1 && X.lat_on) {
-        X.lat = dr_latency(cl, A.seed, env, dr_step, (uint32_t)dr_reset_key, (A.nsub < 0) ? P->substeps : A.nsub);
+        X.lat = (!HP || cl.enabled) ? dr_latency(cl, A.seed, env, dr_step, (uint32_t)dr_reset_key, (A.nsub < 0) ? P->substeps : A.nsub) : 0;
+        if (HP && held(R_ACT + 2)) X.lat = (int)hp[(size_t)(R_ACT + 2) * N + env];      // whole and in [0, substeps]: lm_set_env_params checked it
         if (active && limb == 0) arec[(size_t)2 * N + env] = (float)X.lat;
       }
     }

@@ -253,6 +253,9 @@ class EngineParams:
     # ---- per-foot contact-force reporting (sim.engine.contact_forces): not part of the C parameter block - the task switches it on
     # with Engine.enable_contact_forces() after creating the engine, when any of its blocks asks for it
     contact_forces: bool = False
+    # ---- per-env parameters held by the caller (sim.engine.env_params): not part of the C parameter block either - the task creates
+    # its blocks with dr_enabled (no channel on unless domain_randomization.randomize says so) and calls Engine.enable_env_params() before the first step
+    env_params: bool = False
     # ---- bookkeeping
     max_reset_counts: int = 2048        # success-rate window (quadruped_pose_control.py:151)
     # values the -1 sentinels above were resolved to ({field: value}).  dataclasses.replace() hands every field back to __init__, the resolved ones

@@ -27,9 +27,44 @@ EPISODE_ROWS = 9         # LM_EPISODE_ROWS (include/lm_policy.h)
 EPISODE = dict(running_return=0, running_length=1, episodes=2, sum_return=3, sum_length=4, goal=5, timeout=6, failure=7, last_return=8)
 TRAJ_COLS, TRAJ_MAX_ENVS = 64, 256      # LM_TRAJ_COLS, LM_TRAJ_MAX_ENVS (include/lm_policy.h)
 PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS, PTR_CONTACT, PTR_DR_ACTUATOR = range(14)
+PTR_ENV_PARAMS = 14      # LM_PTR_ENV_PARAMS
+ENV_PARAM_ROWS = DR_PHYS_ROWS + DR_MASS_ROWS + DR_ACTUATOR_ROWS      # LM_ENV_PARAM_ROWS = 69: the three records one after the other
+# the hold table of Engine.enable_env_params() by name: (first row, rows); one row gives a (N,) view, several a (rows, N) one.  The layouts are
+# those of dr_phys + dr_mu, dr_mass and dr_actuator; body_masses is in RobotModel.table_body_order()
+ENV_PARAMS = dict(max_efforts=(0, 12), max_velocities=(12, 12), gravity=(24, 3), base_force=(27, 3), joint_damping=(30, 12), mu=(DR_PHYS_MU, 1),
+                  plate_mass=(DR_PHYS_ROWS, 1), plate_inertia_factor=(DR_PHYS_ROWS + 1, 1), body_masses=(DR_PHYS_ROWS + 2, NUM_BODIES),
+                  kp=(DR_PHYS_ROWS + DR_MASS_ROWS, 1), kd=(DR_PHYS_ROWS + DR_MASS_ROWS + 1, 1), latency=(DR_PHYS_ROWS + DR_MASS_ROWS + 2, 1))
+
+
+def env_param_rows(name: str):
+    """(row0, nrows) of a named group of the hold table; ValueError for a name that is none of ENV_PARAMS."""
+    if name not in ENV_PARAMS:
+        raise ValueError(f"unknown env parameter {name!r}: one of {sorted(ENV_PARAMS)}")
+    return ENV_PARAMS[name]
+
+
+def env_param_shape(name: str, num_envs: int):
+    """Shape of the values Engine.set_env_params(name=...) takes: (N,) for a one-row group, (rows, N) otherwise."""
+    _, n = env_param_rows(name)
+    return (int(num_envs),) if n == 1 else (n, int(num_envs))
+
+
+def env_param_values(name: str, values, num_envs: int) -> np.ndarray:
+    """`values` as the contiguous host float32 (nrows, N) block lm_set_env_params takes; a python scalar holds every env at that value.
+    ValueError for an unknown name or a shape other than env_param_shape(name, N)."""
+    row0, n = env_param_rows(name)
+    if hasattr(values, "detach"):
+        values = values.detach().cpu().numpy()
+    a = np.asarray(values, dtype=np.float32)
+    want = env_param_shape(name, num_envs)
+    if a.ndim == 0:
+        a = np.full(want, float(a), dtype=np.float32)
+    if tuple(a.shape) != want:
+        raise ValueError(f"env parameter {name!r}: values of shape {want} are needed (SoA: one row per component, one column per env), got {tuple(a.shape)}")
+    return np.ascontiguousarray(a.reshape(n, int(num_envs)))
 
 # names of the exported C symbols (checked by tests/test_abi.py against include/lm_engine.h)
-EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass_randomization", "lm_set_actuator_randomization", "lm_enable_contact_forces", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
+EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass_randomization", "lm_set_actuator_randomization", "lm_enable_contact_forces", "lm_enable_env_params", "lm_set_env_params", "lm_clear_env_params", "lm_env_params_held", "lm_step", "lm_post_physics", "lm_reset_all", "lm_task_eval", "lm_apply_resets", "lm_substeps",
            "lm_forward_kinematics", "lm_debug_dynamics", "lm_ptr", "lm_num_envs", "lm_num_obs", "lm_set_seed", "lm_last_error", "lm_version", "lm_abi_version",
            "lm_gnn_param_count", "lm_gnn_forward", "lm_mlp_param_count", "lm_mlp_forward", "lm_mlp_param_count_obs", "lm_mlp_forward_obs",
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy",
@@ -209,7 +244,7 @@ def hipcc_command(extra, out):
     # -amdgpu-mfma-vgpr-form: the MFMA accumulators of the policy tiles live in ordinary VGPRs, so the VALU work on them (ELU, max aggregation,
     # LDS stores) needs no v_accvgpr_read per element (504 of them in k_gnn_forward)
     return [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
-            "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_h2.hip"), os.path.join(_CSRC, "lm_engine_h3.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"), os.path.join(_CSRC, "lm_engine_tr.hip"),
+            "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_h2.hip"), os.path.join(_CSRC, "lm_engine_h3.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"), os.path.join(_CSRC, "lm_engine_tr.hip"), os.path.join(_CSRC, "lm_engine_hp.hip"),
             os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), os.path.join(_CSRC, "lm_gnn_ppo.hip"), os.path.join(_CSRC, "lm_optim.hip"), "-o", out]
 
 
@@ -246,6 +281,10 @@ def load_library() -> C.CDLL:
     lib.lm_set_mass_randomization.argtypes = [vp, ip, C.POINTER(LmMassDr)]
     lib.lm_set_actuator_randomization.argtypes = [vp, ip, C.POINTER(LmActuatorDr)]
     lib.lm_enable_contact_forces.argtypes = [vp, ip]
+    lib.lm_enable_env_params.argtypes = [vp]
+    lib.lm_set_env_params.argtypes = [vp, ip, ip, fp]
+    lib.lm_clear_env_params.argtypes = [vp, ip, ip]
+    lib.lm_env_params_held.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.lm_step.argtypes = [vp, fp, fp, fp, fp, fp, fp, fp, vp]
     lib.lm_post_physics.argtypes = [vp, fp, fp, fp, fp, fp, fp, vp]
     lib.lm_reset_all.argtypes = [vp, vp]
@@ -428,6 +467,61 @@ class Engine:
         """float (N, 4) view: the share of the last step's sub-steps in which each foot was loaded (lam_n > 0), a multiple of 1 / n_sub."""
         return self._contact_record()[12:16].T
 
+    # ------------------------------------------------------------------ per-env parameters held by the caller (DESIGN.md 3.6)
+    def enable_env_params(self):
+        """Allocate the hold table (nothing held): from now on step() launches the builds of the randomised kernels that apply held rows.
+        Randomised engines only (dr_enabled, with or without channels); not together with contact-force reporting."""
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib.lm_enable_env_params(self._h))
+
+    @property
+    def env_params_enabled(self) -> bool:
+        return bool(self.lib.lm_ptr(self._h, PTR_ENV_PARAMS))
+
+    def _env_table(self):
+        return self._record("env_params", PTR_ENV_PARAMS, ENV_PARAM_ROWS, "env params are not enabled on this engine: call enable_env_params() first "
+                            "(task YAML: sim.engine.env_params: true)")
+
+    def set_env_params(self, **named):
+        """Hold the named groups (ENV_PARAMS) at per-env values: SoA arrays / tensors of env_param_shape(name, N), or a scalar for every env.
+        Every later step uses them in place of what the group's channel draws (or of the nominal value); the dr_* records report them.
+        Validated by the library (EngineError, nothing changed) - finite; masses, plate_inertia_factor, kp, kd > 0; mu, max_efforts,
+        max_velocities, joint_damping >= 0; latency whole in [0, substeps]; groups the engine's blocks do not read are refused.  Names and
+        shapes of all groups are checked first (ValueError); each group is then one library call, so the groups in front of a refused one
+        stay held."""
+        blocks = [(env_param_rows(k)[0], env_param_values(k, v, self.num_envs)) for k, v in named.items()]      # every name and shape first
+        self._env_table()
+        with self.torch.cuda.device(self.device):
+            for row0, a in blocks:
+                self._check(self.lib.lm_set_env_params(self._h, row0, a.shape[0], a.ctypes.data_as(C.c_void_p)))
+
+    def clear_env_params(self, *names):
+        """The named groups follow their channel (or the nominal value) again; without names, all of them."""
+        spans = [env_param_rows(k) for k in names] or [(0, ENV_PARAM_ROWS)]
+        self._env_table()
+        with self.torch.cuda.device(self.device):
+            for row0, n in spans:
+                self._check(self.lib.lm_clear_env_params(self._h, row0, n))
+
+    def env_params_mask(self):
+        """bool (69,) numpy array: which rows of the hold table are held."""
+        m = (C.c_uint64 * 2)()
+        self._check(self.lib.lm_env_params_held(self._h, m))
+        return np.array([(int(m[r >> 6]) >> (r & 63)) & 1 for r in range(ENV_PARAM_ROWS)], dtype=bool)
+
+    @property
+    def env_params_held(self):
+        """Names of the groups that are held (every row of the group)."""
+        m = self.env_params_mask()
+        return [k for k, (r0, n) in ENV_PARAMS.items() if m[r0:r0 + n].all()]
+
+    @property
+    def env_params(self):
+        """dict name -> zero-copy view of the hold table ((N,) or (rows, N), ENV_PARAMS).  Rows that are not held read as what was last held
+        there (zeros at first); change values through set_env_params, which validates them."""
+        t = self._env_table()
+        return {k: (t[r0] if n == 1 else t[r0:r0 + n]) for k, (r0, n) in ENV_PARAMS.items()}
+
     @property
     def dr_actuator(self):
         """float [3][N]: what the last step used - row 0 the position gain kp, row 1 the velocity gain kd (both floored), row 2 the command
@@ -580,8 +674,11 @@ class Engine:
     def state_dict(self):
         """Everything lm_step reads besides its arguments: SoA state, counters, success windows, randomisation counters (host tensors)."""
         self.torch.cuda.synchronize(self.device)
-        return {"state": self.state.cpu().clone(), "cnt": self.cnt.cpu().clone(), "stats": self._stats_i32.cpu().clone(),
-                "dr_cnt": self.dr_cnt.cpu().clone(), "num_envs": self.num_envs, "seed": self.seed}
+        sd = {"state": self.state.cpu().clone(), "cnt": self.cnt.cpu().clone(), "stats": self._stats_i32.cpu().clone(),
+              "dr_cnt": self.dr_cnt.cpu().clone(), "num_envs": self.num_envs, "seed": self.seed}
+        if self.env_params_enabled:          # the hold table and which of its rows are held (absent on engines that never enabled it)
+            sd["env_params"] = {"table": self._env_table().cpu().clone(), "mask": self.torch.from_numpy(self.env_params_mask())}
+        return sd
 
     def load_state_dict(self, sd):
         assert int(sd["num_envs"]) == self.num_envs and tuple(sd["state"].shape) == tuple(self.state.shape)
@@ -589,6 +686,21 @@ class Engine:
         self._stats_i32.copy_(sd["stats"].to(self.device)); self.dr_cnt.copy_(sd["dr_cnt"].to(self.device))
         if "seed" in sd:          # goal sampling / domain randomisation are keyed by the seed: a resumed engine must carry the checkpoint's
             self.set_seed(int(sd["seed"]))
+        if "env_params" in sd:    # held rows go through the validating setter, in runs of adjacent rows; the others are cleared
+            self.enable_env_params()
+            table = np.ascontiguousarray(sd["env_params"]["table"].cpu().numpy(), dtype=np.float32); mask = np.asarray(sd["env_params"]["mask"].cpu().numpy(), dtype=bool)
+            assert table.shape == (ENV_PARAM_ROWS, self.num_envs) and mask.shape == (ENV_PARAM_ROWS,)
+            with self.torch.cuda.device(self.device):
+                self._check(self.lib.lm_clear_env_params(self._h, 0, ENV_PARAM_ROWS))
+                r = 0
+                while r < ENV_PARAM_ROWS:
+                    if not mask[r]:
+                        r += 1; continue
+                    r1 = r
+                    while r1 < ENV_PARAM_ROWS and mask[r1]:
+                        r1 += 1
+                    self._check(self.lib.lm_set_env_params(self._h, r, r1 - r, table[r:r1].ctypes.data_as(C.c_void_p)))
+                    r = r1
 
 
 POLICY_MLP, POLICY_GNN = 0, 1
@@ -765,6 +877,20 @@ class EpisodeRecord:
         if split:
             out["loco"] = self._reduce(rec[:, :split]); out["mani"] = self._reduce(rec[:, split:])
         return out
+
+    def summary_by(self, groups):
+        """The same host reduction per group: `groups` is an int (N,) array / tensor of group ids; returns {id: summary of the envs with that
+        id}, ids ascending (what an evaluation sweep reads: one group per grid point)."""
+        return EpisodeRecord.reduce_by(self.record.detach().cpu().double().numpy(), groups)
+
+    @staticmethod
+    def reduce_by(rec, groups):
+        if hasattr(groups, "detach"):
+            groups = groups.detach().cpu().numpy()
+        g = np.asarray(groups)
+        if g.shape != (rec.shape[1],) or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError(f"groups: an integer array of shape ({rec.shape[1]},) is needed, got {g.dtype} {g.shape}")
+        return {int(k): EpisodeRecord._reduce(rec[:, g == k]) for k in np.unique(g)}
 
 
 class TrajectoryRecord:

@@ -100,6 +100,8 @@ class RLTask:
                                          float(self.clip_obs), float(self.clip_actions))
         if any(getattr(p, "contact_forces", False) for p in params):      # sim.engine.contact_forces: before the first step
             self.engine.enable_contact_forces(True)
+        if any(getattr(p, "env_params", False) for p in params):          # sim.engine.env_params: before the first step
+            self.engine.enable_env_params()
         self.cleanup()
         return self.engine
 
@@ -121,6 +123,8 @@ class RLTask:
     def goal_quaternions(self): return self.engine.state[86:90].T
     @property
     def contact_forces(self): return self.engine.contact_forces            # (N, 4, 3) world-frame force on each foot, N; needs sim.engine.contact_forces
+    def set_env_params(self, **named): self.engine.set_env_params(**named)      # hold per-env physics parameters (needs sim.engine.env_params; Engine.set_env_params)
+    def clear_env_params(self, *names): self.engine.clear_env_params(*names)
     @property
     def contact_fraction(self): return self.engine.contact_fraction        # (N, 4) share of the step's sub-steps with the foot loaded
     @property

@@ -156,6 +156,8 @@ class _QuadrupedTask(RLTask):
                         cc_update_last_tgt=int(self.update_last_targets))
         base.update(mat_fields)
         base.update(self._dr_randomizer.engine_dr(kw.get("mode", MODE_LOCO)))
+        if bool(eng.get("env_params", False)):      # per-env parameters held by the caller: the randomised kernels carry them, so the block is
+            base.update(env_params=True, dr_enabled=1)      # created with dr_enabled even when randomize is false - no channel on, no observation or action noise
         if any(ch.enabled for ch in base.get("dr_mat", [])) and base["friction_combine"] < 0:
             raise ValueError(f"sim.engine.friction_combine {comb!r}: one of {sorted(FRICTION_COMBINE)} is needed with material_properties randomisation")
         base.update(kw)

@@ -6,7 +6,10 @@ min_frequency 0: every reset draws; and behind the YAML's min_frequency, which o
 task's own randomised leg), and what the actuator channels add (joint_kps + joint_kds + command_latency on QuadrupedPoseControlCustomController,
 drawn once per env / redrawn every step, against that task's own randomised leg; joint_kds alone on QuadrupedPoseControl).  Leg names given on
 the command line restrict the run to those legs (ratios are printed for the pairs that ran).  `resets_per_step` is the mean number of envs
-reset per timed step of each leg."""
+reset per timed step of each leg.
+The leg `env_params` is a comparison of its own: the randomised task beside the same task with env params enabled and nothing held
+(k_step_dr against k_step_dr_hp) and with every row its block reads held at what the first step recorded - three engines in one process, timed in turn,
+200 steps a turn, 24 turns each; median and quartiles of the turns under "env_params"."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -30,6 +33,42 @@ ACTUATOR = lambda t, **kw: {"articulation_views": {"robot_view": {"joint_kps": _
 JOINT_KDS = lambda e: {"articulation_views": {"robot_view": {"joint_kds": e}}}
 only = set(sys.argv[1:])
 resets = {}
+
+
+def env_params_legs(turns=24, steps=200, N=4096):
+    import numpy as np
+    RAND = {"domain_randomization": {"randomize": True}}
+    legs = {"randomised": {"task": RAND}, "env_params_nothing_held": {"task": {**RAND, "sim": {"engine": {"env_params": True}}}},
+            "env_params_all_held": {"task": {**RAND, "sim": {"engine": {"env_params": True}}}}}
+    envs = {k: lm.make_env("QuadrupedPoseControl", num_envs=N, overrides=ov) for k, ov in legs.items()}
+    g = torch.Generator(device="cuda").manual_seed(0)
+    pool = [torch.rand(N, 12, device="cuda", generator=g) * 2 - 1 for _ in range(16)]
+    o = (torch.empty(N, 64, device="cuda"), torch.empty(N, 93, device="cuda"), torch.empty(N, device="cuda"), torch.empty(N, dtype=torch.int64, device="cuda"), torch.empty(13, device="cuda"))
+    for k, env in envs.items():
+        e = env._task.engine
+        for t in range(50): e.step(pool[t % 16], None, *o)
+        torch.cuda.synchronize()
+        if k == "env_params_all_held":
+            e.set_env_params(max_efforts=e.dr_phys[0:12], max_velocities=e.dr_phys[12:24], gravity=e.dr_phys[24:27], base_force=e.dr_phys[27:30],
+                             joint_damping=e.dr_phys[30:42], mu=e.dr_mu, body_masses=e.dr_body_masses, kd=e.dr_kd)
+    us = {k: [] for k in envs}
+    for turn in range(turns):
+        for k, env in envs.items():
+            e = env._task.engine
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for t in range(steps): e.step(pool[t % 16], None, *o)
+            torch.cuda.synchronize(); us[k].append((time.perf_counter() - t0) / steps * 1e6)
+    held = len(envs["env_params_all_held"]._task.engine.env_params_mask().nonzero()[0])
+    for env in envs.values(): env.close()
+    q = lambda v: dict(zip(("q1", "median", "q3"), (float(x) for x in np.percentile(v, [25, 50, 75]))))
+    out = {k: q(v) for k, v in us.items()}
+    out.update(turns=turns, steps_per_turn=steps, num_envs=N, rows_held=held,
+               nothing_held_overhead=out["env_params_nothing_held"]["median"] / out["randomised"]["median"] - 1,
+               all_held_overhead=out["env_params_all_held"]["median"] / out["randomised"]["median"] - 1)
+    return out
+
+
+env_params = env_params_legs() if (not only or "env_params" in only) else None
 for name, ov in (("plain", None), ("randomised", {"task": {"domain_randomization": {"randomize": True}}}),
                  ("randomised_material", {"task": {"domain_randomization": {"randomize": True, "randomization_params": MATERIAL}}}),
                  ("randomised_min_frequency_0", {"task": {"domain_randomization": {"randomize": True, "min_frequency": 0}}}),
@@ -72,4 +111,4 @@ print(json.dumps({"us_per_step": res, "overhead": ratio("randomised", "plain"),
                   "actuator_startup_overhead_on_k_step_dr_pd": ratio("cc_randomised_actuator_startup", "cc_randomised"),
                   "actuator_every_step_overhead_on_k_step_dr_pd": ratio("cc_randomised_actuator_every_step", "cc_randomised"),
                   "joint_kds_every_step_overhead_on_k_step_dr": ratio("randomised_joint_kds_every_step", "randomised"),
-                  "resets_per_step": resets}))
+                  "env_params": env_params, "resets_per_step": resets}))

@@ -4,12 +4,15 @@ the first --episodes-per-env episodes of every env, one JSON line with the summa
 timeout_rate, failure_rate, ...; co-training tasks also per half).
     python tools/eval_policy.py --checkpoint agent.pt --task QuadrupedPoseControl [--num-envs 4096 --episodes-per-env 1 --stochastic --randomize]
 --record-envs 0,2048 --record-dir DIR also writes, per listed env, DIR/<task>_env<e>.npy (the first episode's joint positions, float32 (L, 12):
-the format of the reference's RECORD_JOINT files) and DIR/<task>_env<e>.npz (every column of the trajectory record), and names them in the JSON line."""
+the format of the reference's RECORD_JOINT files) and DIR/<task>_env<e>.npz (every column of the trajectory record), and names them in the JSON line.
+--sweep NAME=LO:HI:K (repeatable; several form their Cartesian product) holds a grid of per-env physics parameters - NAME one of mu, body_mass_scale,
+base_mass_add, plate_mass, kp_scale, kd_scale, latency, max_effort - with env e at grid point e % K_total, and adds "sweep" to the JSON line: per point
+its values and the summary of its envs (episodes, success_rate, mean_return, ...): a robustness curve from one launch per step."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import locomanipulationrl_amd as lm
-from locomanipulationrl_amd.train.evaluate import evaluate
+from locomanipulationrl_amd.train.evaluate import evaluate, parse_sweep, sweep_env_params, sweep_grid, sweep_groups, sweep_nominals
 from locomanipulationrl_amd.train.ppo import RunningStandardScaler
 
 
@@ -24,14 +27,22 @@ def main():
     ap.add_argument("--record-envs", default=None, help="comma-separated env ids whose trajectories are recorded")
     ap.add_argument("--record-dir", default=None, help="where the recorded trajectories are written (needs --record-envs)")
     ap.add_argument("--record-rows", type=int, default=None, help="rows kept per recorded env (default: max_episode x episodes per env)")
+    ap.add_argument("--sweep", action="append", default=[], metavar="NAME=LO:HI:K", help="hold a grid of per-env parameters (repeatable: Cartesian product)")
     a = ap.parse_args()
+    try:
+        points = sweep_grid([parse_sweep(x) for x in a.sweep]) if a.sweep else None
+        groups = sweep_groups(a.num_envs, len(points)) if points else None
+    except ValueError as e:
+        raise SystemExit(str(e))
     record_envs = [int(x) for x in a.record_envs.split(",")] if a.record_envs else None
     if (record_envs is None) != (a.record_dir is None):
         raise SystemExit("--record-envs and --record-dir go together")
     sd = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     torch.manual_seed(a.seed)
     env = lm.make_env(a.task, num_envs=a.num_envs, seed=a.seed,
-                      overrides={"task": {"domain_randomization": {"randomize": True}} if a.randomize else {}})
+                      overrides={"task": {**({"domain_randomization": {"randomize": True}} if a.randomize else {}),
+                                          **({"sim": {"engine": {"env_params": True}}} if points else {})}})
+    held = sweep_env_params(points, groups, **sweep_nominals(env._task)) if points else None
     n_obs = int(env.observation_space.shape[0])
     if int(sd["num_observations"]) != n_obs:
         raise SystemExit(f"the checkpoint was trained on {sd['num_observations']}-wide observations, {a.task} has {n_obs}")
@@ -44,7 +55,10 @@ def main():
     model.load_state_dict(sd["model"]); model = model.to("cuda:0")
     scaler = RunningStandardScaler(n_obs, "cuda:0"); scaler.load_state_dict(sd["obs_scaler"])
     out = evaluate(env, model, scaler, episodes_per_env=a.episodes_per_env, max_steps=a.max_steps, deterministic=not a.stochastic, fused=not a.no_fused,
-                   record_envs=record_envs, record_rows=a.record_rows)
+                   record_envs=record_envs, record_rows=a.record_rows, env_params=held, groups=groups)
+    by_group = out.pop("groups", None)
+    if by_group is not None:
+        out["sweep"] = [{"point": points[g], **by_group[g]} for g in sorted(by_group)]
     traj = out.pop("trajectory", None)
     if traj is not None:
         out["trajectory_files"] = traj.save_npy(a.record_dir, a.task)
