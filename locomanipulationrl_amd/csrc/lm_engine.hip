@@ -41,8 +41,7 @@ extern "C" void lm_dbg_pass2_read(unsigned int* out, int clear) {
 #include "lm_policy_dev.h"
 #include "lm_internal.h"
 #include "lm_step.h"      // the device code of the step: lm_samplers.h, lm_dynamics.h, lm_task.h, lm_step.h
-#include "lm_traj_dev.h"         // RolloutTraj, LM_EV_TRAJ: the persistent builds with a trajectory record (lm_engine_tr.hip)
-#include "lm_rollout_dev.h"      // RolloutDev, step_dispatch, PolicySmem: shared with the evaluation builds (lm_engine_ev.hip)
+#include "lm_rollout_dev.h"      // RolloutDev, step_dispatch, PolicySmem; RolloutEv, RolloutTraj and the launchers of lm_engine_ev.hip / lm_engine_tr.hip
 
 // The step kernels.  One launch per step(); a wavefront picks its specialisation (task mode x actuator family) from the kernel arguments.  The
 // velocity-drive tasks (k_step: the headline) and the PD-actuator families (k_step_pd) are separate kernels, so that the register allocation
@@ -740,6 +739,9 @@ int lm_destroy(lm_engine* h) {
 // the row mask of the hold table sits behind its LM_ENV_PARAM_ROWS x N floats, at the next 8-byte boundary (N may be odd)
 static size_t env_mask_offset(int N) { return ((size_t)LM_ENV_PARAM_ROWS * (size_t)N + 1) & ~(size_t)1; }
 
+// the step kernels' kind of parameter block t: actuator family x task mode (StepArgs::kind, lm_step.h)
+static int block_kind(const lm_engine* h, int t) { return h->h_params[t].variant * 2 + (h->h_params[t].mode == LM_MODE_MANI ? 1 : 0); }
+
 static StepArgs make_args(lm_engine* h, const float* actions, const float* goal_rand, float* out_obs, float* out_states, float* out_rew, int64_t* out_resets) {
   StepArgs A;
   A.params = h->d_params; A.table = h->d_table; A.state = h->d_state; A.cnt = h->d_cnt; A.actions = actions; A.goal_rand = goal_rand;
@@ -749,7 +751,7 @@ static StepArgs make_args(lm_engine* h, const float* actions, const float* goal_
   A.N = h->N; A.split = h->split; A.seed = h->seed; A.skip_reset = 0; A.nsub = -1; A.drc = h->d_drc; A.dr_phys = h->d_dr_phys; A.reset_dr = h->d_reset_dr; A.mass_dr = h->d_mass_dr;
   A.env_params = h->d_env_params; A.contact = h->contact_on ? h->d_contact : nullptr; A.actuator_dr = h->d_actuator_dr;
   A.env_mask = h->d_env_params ? (const uint64_t*)(h->d_env_params + env_mask_offset(h->N)) : nullptr;
-  for (int t = 0; t < 2; t++) A.kind[t] = h->h_params[t].variant * 2 + (h->h_params[t].mode == LM_MODE_MANI ? 1 : 0);
+  for (int t = 0; t < 2; t++) A.kind[t] = block_kind(h, t);
   return A;
 }
 
@@ -771,7 +773,7 @@ extern "C" int lm_debug_stamps(unsigned long long* out) { return hipMemcpyFromSy
 // engines with a locomotion block up to h2_max_envs), 3 = k_step_h3 (two helper wavefronts: the same engines up to h3_max_envs).  Every other
 // engine: 0, the one-wavefront kernel of its family.
 static int step_variant(const lm_engine* h) {
-  const int k0 = h->h_params[0].variant * 2 + (h->h_params[0].mode == LM_MODE_MANI ? 1 : 0), k1 = h->h_params[1].variant * 2 + (h->h_params[1].mode == LM_MODE_MANI ? 1 : 0);
+  const int k0 = block_kind(h, 0), k1 = block_kind(h, 1);
   if (h->contact_on || h->dr_enabled || k0 >= 2 || k1 >= 2) return 0;
   if (k0 == 0 && k1 == 0 && h->N >= h->w2_min_envs) return 1;
   if ((k0 == 0 || k1 == 0) && h->N <= h->h3_max_envs) return 3;
@@ -1121,15 +1123,14 @@ int lm_internal_rollout(lm_engine* h, int policy, const LmRolloutArgs& R, hipStr
   D.rewards = R.rewards; D.dones = R.dones; D.acc_steps = R.acc_steps; D.T = R.T; D.noise_seed = R.noise_seed;
   static const bool streaming = getenv("LM_ROLLOUT_STREAMING_MLP") != nullptr;      // kernel experiments: the four-wavefront tile with streamed weights
   const int ev = (R.deterministic ? LM_EV_DET : 0) | (R.record ? LM_EV_REC : 0);
+  RolloutEv E; E.record = R.record; E.cap = R.episode_cap;
   if (R.traj_K) {      // builds that keep a trajectory record (lm_engine_tr.hip)
     if (!lm_internal_rollout_trajectories(policy, R.nobs, R.deterministic, R.record != nullptr)) return fail(-1, "persistent rollout: no build keeps a trajectory record for this policy / observation width / switches; such plans run through the graph mode");
-    RolloutEv E; E.record = R.record; E.cap = R.episode_cap;
     RolloutTraj TJ; TJ.ids = R.traj_ids; TJ.rows = R.traj_rows; TJ.header = R.traj_header; TJ.K = R.traj_K; TJ.max_rows = R.traj_max_rows; TJ.cap = R.traj_cap;
     if (lm_internal_launch_rollout_tr(&A, &D, &E, &TJ, ev | LM_EV_TRAJ, policy, R.nobs, h->nblocks, s)) return -1;
   }
   else if (ev) {      // evaluation builds (lm_engine_ev.hip; the MLP always on the resident tile)
     if (R.record && !lm_internal_rollout_records(policy, R.nobs)) return fail(-1, "persistent rollout: no recording build for this policy / observation width; recording plans run through the graph mode");
-    RolloutEv E; E.record = R.record; E.cap = R.episode_cap;
     if (lm_internal_launch_rollout_ev(&A, &D, &E, ev, policy, R.nobs, h->nblocks, s)) return -1;
   }
   else if (policy == LM_POLICY_MLP && R.nobs == 64 && !streaming) hipLaunchKernelGGL(k_rollout_mlp<64>, dim3(h->nblocks), dim3(256), 0, s, A, D);

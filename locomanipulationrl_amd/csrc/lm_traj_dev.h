@@ -1,6 +1,6 @@
 // lm_traj_dev.h -- the trajectory record of include/lm_policy.h on the device: the column map of a row and the update of one slot by one
 // wavefront (lane = column), used by k_trajectory_update (lm_policy.hip); the column map also by the persistent builds that record
-// (lm_engine_tr.hip), whose argument block and host hooks are declared here too.
+// (lm_engine_tr.hip; their device code and host hooks are in lm_rollout_dev.h), whose flag bit and argument block are declared here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,12 +22,6 @@ static_assert(LM_TRAJ_COLS == 64, "one lane of a wavefront per column");
 // RolloutEv (StepArgs, SampleArgs and RolloutDev keep their size).
 #define LM_EV_TRAJ 4
 struct RolloutTraj { const int32_t* ids; float* rows; int32_t* header; int K, max_rows, cap; };
-struct StepArgs; struct RolloutDev; struct RolloutEv;
-// 1 when lm_engine_tr.hip has a build for these ev bits (LM_EV_TRAJ among them) / policy / observation width
-extern "C" __attribute__((visibility("hidden"))) int lm_internal_rollout_tr_built(int ev, int policy, int nobs);
-// launches it: 0, or -1 when there is no such build
-extern "C" __attribute__((visibility("hidden"))) int lm_internal_launch_rollout_tr(const StepArgs* A, const RolloutDev* D, const RolloutEv* E, const RolloutTraj* TJ, int ev,
-                                                                                  int policy, int nobs, int nblocks, hipStream_t s);
 
 // column c of a row -> the state row it copies (fb: R_FB0 or R_FB1 of the env's block), or -1 for columns 59..63 (step outputs and counters)
 __device__ __forceinline__ int traj_state_row(int c, int fb) {
