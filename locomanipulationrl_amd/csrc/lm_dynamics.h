@@ -396,8 +396,14 @@ LM_DEV void integrate_free(FreeBody& F, const M3& R, float dt) {
 // k_step_h2 (lm_engine_h2.hip): a second wavefront of the workgroup computes the limb bias terms (see helper_wave below).  The two wavefronts
 // exchange 16 + 9 floats per lane and sub-step through seven more slots of the same [slot][lane] array.  k_step_h3 (lm_engine_h3.hip,
 // LM_HELPER_WAVE 2) has a third wavefront for the contact terms (helper_wave_terms): it reads the same four slots, with the base height in
-// the last word, and writes stash slots 7-15 themselves
+// the last word, and writes stash slots 7-15 themselves.  The task-layer state that wavefront 1 fetches during the last sub-step
+// (helper_task_state, lm_step.h) has five slots of its own, TASK_SLOT: a second pass of that sub-step still reads slots 0-18 and HAND_OUT
+#if LM_HELPER_WAVE >= 2
+#define STASH_SLOTS 34
+#define TASK_SLOT 29          // 5 slots, wavefront 1 -> wavefront 0: succ, consec, greset, reset | progress, episode, lact | lact, lqd | ltip, goal | goal
+#else
 #define STASH_SLOTS 29
+#endif
 #define HAND_IN 22            // 4 slots, wavefront 0 -> helpers: q, qd | qd, u.w | u.w, u.v | row 2 of the base's rotation (k_step_h3: and the base height)
 #define HAND_OUT 26           // 3 slots, helper -> wavefront 0: fcs | fcs, hq | hq
 #define LM_STEP_ATTR

@@ -50,6 +50,52 @@ extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_h2
 extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_h3(const StepArgs* A, int nblocks, hipStream_t s);      // k_step_h3's launcher (lm_engine_h3.hip), called by lm_step
 extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_hp(const StepArgs* A, int pd, int nblocks, hipStream_t s);      // k_step_dr_hp / k_step_dr_pd_hp's launcher (lm_engine_hp.hip), called by lm_step
 
+// The task-layer state of one lane at the start of a step: the counters and the last action / joint rate / tip / goal from memory, and for an env
+// that is reset in this step the values reset_idx gives them, the new goal drawn from goal_rand or the hash, and the next episode number.  It
+// depends only on what is in memory at kernel entry and on the kernel arguments.  Every step kernel runs it behind the physics (issuing the
+// loads at the top of the last sub-step was measured and gains nothing); in k_step_h3 wavefront 1 runs it while wavefront 0 is in the
+// second half of the last sub-step (helper_task_state)
+// (a macro on the caller's own locals - st, cnt, N, env, limb, jj, do_reset, pd, MODE, A, P; S, episode, lqd - and not a function: called as a
+// function from step_body it moved the instructions of the other step kernels, which tools/isa_diff.py does not allow)
+#define LM_TASK_STATE_LOAD \
+  S.succ = (int)cnt[0 * (size_t)N + env]; S.consec = (int)cnt[1 * (size_t)N + env]; S.greset = (int)cnt[2 * (size_t)N + env]; \
+  S.reset = (int)cnt[3 * (size_t)N + env]; S.progress = (int)cnt[4 * (size_t)N + env]; episode = (int)cnt[5 * (size_t)N + env]; \
+_Pragma("unroll") \
+  for (int a = 0; a < 3; a++) { S.lact[a] = st[(size_t)(R_LACT + jj[a]) * N + env]; lqd[a] = st[(size_t)(R_LQD + jj[a]) * N + env]; } \
+  S.ltip = v3(st[(size_t)(R_LTIP + 3 * limb) * N + env], st[(size_t)(R_LTIP + 3 * limb + 1) * N + env], st[(size_t)(R_LTIP + 3 * limb + 2) * N + env]); \
+  S.goal.w = st[(size_t)(R_GOAL + 0) * N + env]; S.goal.x = st[(size_t)(R_GOAL + 1) * N + env]; S.goal.y = st[(size_t)(R_GOAL + 2) * N + env]; S.goal.z = st[(size_t)(R_GOAL + 3) * N + env]; \
+  S.lrd = 0.f; S.ltgt[0] = S.ltgt[1] = S.ltgt[2] = 0.f; \
+  if (pd) { \
+_Pragma("unroll") \
+    for (int a = 0; a < 3; a++) S.ltgt[a] = st[(size_t)(R_LTGT + jj[a]) * N + env]; \
+    S.lrd = st[(size_t)R_LRD * N + env]; \
+  } \
+  if (do_reset) { \
+    float u3[3]; \
+    if (A.goal_rand) { u3[0] = A.goal_rand[(size_t)env * 3]; u3[1] = A.goal_rand[(size_t)env * 3 + 1]; u3[2] = A.goal_rand[(size_t)env * 3 + 2]; } \
+    else hash_uniform3(A.seed, (uint32_t)env, (uint32_t)episode, u3); \
+    S.goal = quat_from_euler(P->goal_lo[0] + (P->goal_hi[0] - P->goal_lo[0]) * u3[0], P->goal_lo[1] + (P->goal_hi[1] - P->goal_lo[1]) * u3[1], \
+                             P->goal_lo[2] + (P->goal_hi[2] - P->goal_lo[2]) * u3[2]); \
+_Pragma("unroll") \
+    for (int a = 0; a < 3; a++) { S.lact[a] = 0.f; lqd[a] = 0.f; } \
+    S.ltip = v3(P->default_tip[3 * limb], P->default_tip[3 * limb + 1], P->default_tip[3 * limb + 2]); \
+    S.succ = 0; S.consec = 0; S.greset = 0; S.reset = 0; S.progress = 0; episode += 1; \
+    if (pd) { \
+_Pragma("unroll") \
+      for (int a = 0; a < 3; a++) S.ltgt[a] = P->init_q[jj[a]]; \
+      Q4 qb; qb.w = (MODE == 0) ? P->init_base_quat[0] : 1.f; qb.x = (MODE == 0) ? -P->init_base_quat[1] : 0.f; \
+      qb.y = (MODE == 0) ? -P->init_base_quat[2] : 0.f; qb.z = (MODE == 0) ? -P->init_base_quat[3] : 0.f; \
+      Q4 d4 = qmul(qb, qconj(S.goal)); \
+      S.lrd = 2.0f * asinf(fminf(sqrtf(d4.x * d4.x + d4.y * d4.y + d4.z * d4.z), 1.0f)); \
+    } \
+  }
+template <int MODE, int VAR>
+LM_DEV void task_state_load(const StepArgs& A, const lm_params* __restrict__ P, float* st, int64_t* cnt, int N, int env, int limb, const int (&jj)[3],
+                            bool do_reset, TaskState& S, int& episode, float (&lqd)[3]) {
+  constexpr bool pd = (VAR >= 1);
+  LM_TASK_STATE_LOAD
+}
+
 // REG0: substep()'s first drive pass runs on registers (1, the step kernels) or reads the stash back like the second (0: k_step_w2 and the
 // persistent rollouts, whose register budget has no room for it; same arithmetic, same bits)
 // HW: wavefront 0 of k_step_h2, whose helper wavefront computes the limb bias terms of every sub-step (helper_wave, lm_dynamics.h)
@@ -57,7 +103,9 @@ extern "C" __attribute__((visibility("hidden"))) void lm_internal_launch_step_hp
 // staged obs / states of a full wavefront out (write_outputs, helper_write_outputs)
 // HP: the randomised step of an engine with caller-held per-env parameters (lm_enable_env_params; k_step_dr_hp / k_step_dr_pd_hp, DR = 1 only): the
 // value of every held row of A.env_params replaces what the channels produced, before the record rows are written.  The mask is wave-uniform
-template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0, int REG0 = 1, int HW = 0, int OW = 0, int HP = 0>
+// TS (wavefront 0 of k_step_h3 only, HW 2; LM_H3_TAIL_STATE): the task-layer state comes from LDS, where wavefront 1 put it during the last
+// sub-step (helper_task_state)
+template <int MODE, int VAR, int DR, int DEFER = 0, int CF = 0, int REG0 = 1, int HW = 0, int OW = 0, int HP = 0, int TS = 0>
 LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float* sTab, float* sObs, float* sSt, float4* sStash) {
   TableRegs TR; table_fetch(A.table, threadIdx.x, TR);
   const int lane = threadIdx.x, limb = lane & 3, envl = lane >> 2;
@@ -306,37 +354,7 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
   if (CF) store_contact(A.contact, N, env, limb, active, cf, nsub, P->dt);      // nsub = 0 (lm_post_physics): the record is left as it was
   // ---- task-layer state (loaded after the physics: issuing these loads at the top of the last sub-step was measured and gains nothing)
   TaskState S; int episode; float lqd[3];
-  S.succ = (int)cnt[0 * (size_t)N + env]; S.consec = (int)cnt[1 * (size_t)N + env]; S.greset = (int)cnt[2 * (size_t)N + env];
-  S.reset = (int)cnt[3 * (size_t)N + env]; S.progress = (int)cnt[4 * (size_t)N + env]; episode = (int)cnt[5 * (size_t)N + env];
-#pragma unroll
-  for (int a = 0; a < 3; a++) { S.lact[a] = st[(size_t)(R_LACT + jj[a]) * N + env]; lqd[a] = st[(size_t)(R_LQD + jj[a]) * N + env]; }
-  S.ltip = v3(st[(size_t)(R_LTIP + 3 * limb) * N + env], st[(size_t)(R_LTIP + 3 * limb + 1) * N + env], st[(size_t)(R_LTIP + 3 * limb + 2) * N + env]);
-  S.goal.w = st[(size_t)(R_GOAL + 0) * N + env]; S.goal.x = st[(size_t)(R_GOAL + 1) * N + env]; S.goal.y = st[(size_t)(R_GOAL + 2) * N + env]; S.goal.z = st[(size_t)(R_GOAL + 3) * N + env];
-  S.lrd = 0.f; S.ltgt[0] = S.ltgt[1] = S.ltgt[2] = 0.f;
-  if (pd) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) S.ltgt[a] = st[(size_t)(R_LTGT + jj[a]) * N + env];
-    S.lrd = st[(size_t)R_LRD * N + env];
-  }
-  if (do_reset) {
-    float u3[3];
-    if (A.goal_rand) { u3[0] = A.goal_rand[(size_t)env * 3]; u3[1] = A.goal_rand[(size_t)env * 3 + 1]; u3[2] = A.goal_rand[(size_t)env * 3 + 2]; }
-    else hash_uniform3(A.seed, (uint32_t)env, (uint32_t)episode, u3);
-    S.goal = quat_from_euler(P->goal_lo[0] + (P->goal_hi[0] - P->goal_lo[0]) * u3[0], P->goal_lo[1] + (P->goal_hi[1] - P->goal_lo[1]) * u3[1],
-                             P->goal_lo[2] + (P->goal_hi[2] - P->goal_lo[2]) * u3[2]);
-#pragma unroll
-    for (int a = 0; a < 3; a++) { S.lact[a] = 0.f; lqd[a] = 0.f; }
-    S.ltip = v3(P->default_tip[3 * limb], P->default_tip[3 * limb + 1], P->default_tip[3 * limb + 2]);
-    S.succ = 0; S.consec = 0; S.greset = 0; S.reset = 0; S.progress = 0; episode += 1;
-    if (pd) {      // :371-384
-#pragma unroll
-      for (int a = 0; a < 3; a++) S.ltgt[a] = P->init_q[jj[a]];
-      Q4 qb; qb.w = (MODE == 0) ? P->init_base_quat[0] : 1.f; qb.x = (MODE == 0) ? -P->init_base_quat[1] : 0.f;
-      qb.y = (MODE == 0) ? -P->init_base_quat[2] : 0.f; qb.z = (MODE == 0) ? -P->init_base_quat[3] : 0.f;
-      Q4 d4 = qmul(qb, qconj(S.goal));
-      S.lrd = 2.0f * asinf(fminf(sqrtf(d4.x * d4.x + d4.y * d4.y + d4.z * d4.z), 1.0f));
-    }
-  }
+  if (!(HW == 2 && TS)) { LM_TASK_STATE_LOAD }
   // ---- blow-up guard: the reference only prints NaNs and asserts (quadruped_pose_control.py:550-558); here a non-finite or
   // exploding state is replaced by the reset pose and the env is flagged for reset, so one bad env cannot poison a batch
   int blown = 0;
@@ -355,6 +373,19 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
     }
   }
   LM_STAMP(6);      // task-state loads, reset scatter, blow-up guard
+#if defined(LM_HELPER_WAVE) && LM_HELPER_WAVE >= 2
+  // k_step_h3's tail (TS): behind barrier R1 the task-layer state is in TASK_SLOT, where wavefront 1 put it while this wavefront ran the second
+  // half of the last sub-step; wavefront 1 ends behind R1
+  if (HW == 2 && TS) {
+    hw_barrier();
+    const float4 t0 = St.get(TASK_SLOT), t1 = St.get(TASK_SLOT + 1), t2 = St.get(TASK_SLOT + 2), t3 = St.get(TASK_SLOT + 3), t4 = St.get(TASK_SLOT + 4);
+    S.succ = __float_as_int(t0.x); S.consec = __float_as_int(t0.y); S.greset = __float_as_int(t0.z); S.reset = __float_as_int(t0.w);
+    S.progress = __float_as_int(t1.x); episode = __float_as_int(t1.y); S.lact[0] = t1.z; S.lact[1] = t1.w;
+    S.lact[2] = t2.x; lqd[0] = t2.y; lqd[1] = t2.z; lqd[2] = t2.w;
+    S.ltip = v3(t3.x, t3.y, t3.z); S.goal.w = t3.w; S.goal.x = t4.x; S.goal.y = t4.y; S.goal.z = t4.z;
+    S.lrd = 0.f; S.ltgt[0] = S.ltgt[1] = S.ltgt[2] = 0.f;
+  }
+#endif
   // ---- read-back (robot.py:276-321)
   TaskIn I;
   M3 Rf = quat_to_mat(F.q.w, F.q.x, F.q.y, F.q.z);
@@ -405,6 +436,30 @@ LM_DEV void step_body(const StepArgs& A, const lm_params* __restrict__ P, float*
   write_outputs<DR, DEFER, (VAR == 1) ? LM_MAX_OBS : 64, OW>(P, A.W, N, env0, lane, limb, env, active, S, O, cnt, episode, sObs, sSt, DO);
   LM_STAMP(10);     // the reduction's round trips
 }
+
+#if defined(LM_HELPER_WAVE) && LM_HELPER_WAVE >= 2
+// The tail of k_step_h3's wavefront 1 (LM_H3_TAIL_STATE).  Behind its last sub-step barrier (with no sub-step: at once) it fetches
+// the task-layer state of lane l of wavefront 0, by the lines every step kernel runs (LM_TASK_STATE_LOAD), into TASK_SLOT, passes barrier R1 and
+// ends.  It reads what wavefront 0 reads, and wavefront 0 writes none of it before R1: cnt and the task rows of the state are stored behind the
+// task layer.  Counters travel as their bit patterns.  Same bits as k_step: plain copies of memory, and in a resetting lane the goal quaternion,
+// a complete result of quat_from_euler that k_step holds rounded too and only uses as an operand.  R1 stands in straight-line code in all three
+// wavefronts (the terms helper passes it in front of its output barrier); with the switch off it is compiled in none
+LM_DEV void helper_task_state(const StepArgs& A, const lm_params* __restrict__ P, float4* sStash, int lane) {
+  const int limb = lane & 3, envl = lane >> 2;
+  const int env0 = lm_block() * ENVS_PER_WAVE, envr = env0 + envl, N = A.N;
+  const int env = (envr < N) ? envr : (N - 1);
+  const int jj[3] = {limb, 4 + 2 * limb, 5 + 2 * limb};
+  const bool do_reset = (A.cnt[3 * (size_t)N + env] != 0) && !A.skip_reset;
+  TaskState S; int episode; float lqd[3];
+  task_state_load<0, 0>(A, P, A.state, A.cnt, N, env, limb, jj, do_reset, S, episode, lqd);
+  Stash St; St.base = sStash; St.lane = lane;
+  St.put(TASK_SLOT, __int_as_float(S.succ), __int_as_float(S.consec), __int_as_float(S.greset), __int_as_float(S.reset));
+  St.put(TASK_SLOT + 1, __int_as_float(S.progress), __int_as_float(episode), S.lact[0], S.lact[1]);
+  St.put(TASK_SLOT + 2, S.lact[2], lqd[0], lqd[1], lqd[2]);
+  St.put(TASK_SLOT + 3, S.ltip.x, S.ltip.y, S.ltip.z, S.goal.w); St.put(TASK_SLOT + 4, S.goal.x, S.goal.y, S.goal.z, 0.f);
+  hw_barrier();      // R1
+}
+#endif
 
 // The step kernels.  One launch per step(); a wavefront picks its specialisation (task mode x actuator family) from the kernel arguments.  The
 // velocity-drive tasks (k_step: the headline) and the PD-actuator families (k_step_pd) are separate kernels, so that the register allocation
