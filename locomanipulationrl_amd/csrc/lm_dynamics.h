@@ -271,8 +271,11 @@ LM_DEV void chol6_solve4(const Chol6& C, R4 x[6]) {
 }
 
 // 3x3 block of this lane's contact rows T_i against the B vectors of contact K:  X[r][s] = T_i,r . B_K,s  (K == own limb: the own block)
+// (in two steps: the raw block, and the select of the own block over it.  k_step_h3's helper wavefronts run the first step for wavefront 0,
+// helper_xblocks below, and wavefront 0 the second on what they hand back)
+struct XRaw { float a00; f2 a0t, c0, c1, c2; };      // row 0: column 0, columns (1 | 2); rows (1 | 2): columns 0, 1, 2
 template <int K>
-LM_DEV void pgs_cross_blocks(int limb, const R4 T[6], const R4 X[6], const float Wf[6], float X0[3], f2 X12[3]) {
+LM_DEV void pgs_cross_raw(const R4 T[6], const R4 X[6], XRaw& R) {
   float a00 = 0.f; f2 a0t = sp2(0.f), c0 = sp2(0.f), c1 = sp2(0.f), c2 = sp2(0.f);
 #pragma unroll
   for (int i = 0; i < 6; i++) {
@@ -281,11 +284,19 @@ LM_DEV void pgs_cross_blocks(int limb, const R4 T[6], const R4 X[6], const float
     a00 = fmaf(t0, k0, a00); a0t = fma_(sp2(t0), k12, a0t);                                   // row 0: column 0, columns (1 | 2)
     c0 = fma_(t12, sp2(k0), c0); c1 = fma_(t12, sp2(k12.x), c1); c2 = fma_(t12, sp2(k12.y), c2);      // rows (1 | 2): columns 0, 1, 2
   }
+  R.a00 = a00; R.a0t = a0t; R.c0 = c0; R.c1 = c1; R.c2 = c2;
+}
+template <int K>
+LM_DEV void pgs_cross_select(int limb, const XRaw& R, const float Wf[6], float X0[3], f2 X12[3]) {
   const bool own = (limb == K);
-  X0[0] = own ? Wf[0] : a00; X0[1] = own ? Wf[1] : a0t.x; X0[2] = own ? Wf[2] : a0t.y;
-  X12[0] = mk2(own ? Wf[1] : c0.x, own ? Wf[2] : c0.y);
-  X12[1] = mk2(own ? Wf[3] : c1.x, own ? Wf[4] : c1.y);
-  X12[2] = mk2(own ? Wf[4] : c2.x, own ? Wf[5] : c2.y);
+  X0[0] = own ? Wf[0] : R.a00; X0[1] = own ? Wf[1] : R.a0t.x; X0[2] = own ? Wf[2] : R.a0t.y;
+  X12[0] = mk2(own ? Wf[1] : R.c0.x, own ? Wf[2] : R.c0.y);
+  X12[1] = mk2(own ? Wf[3] : R.c1.x, own ? Wf[4] : R.c1.y);
+  X12[2] = mk2(own ? Wf[4] : R.c2.x, own ? Wf[5] : R.c2.y);
+}
+template <int K>
+LM_DEV void pgs_cross_blocks(int limb, const R4 T[6], const R4 X[6], const float Wf[6], float X0[3], f2 X12[3]) {
+  XRaw R; pgs_cross_raw<K>(T, X, R); pgs_cross_select<K>(limb, R, Wf, X0, X12);
 }
 
 // One Gauss-Seidel turn: contact K relaxes its normal row, then its two friction rows as a pair (both from the state the normal row
@@ -313,7 +324,19 @@ LM_DEV void pgs_turn(float m, const PgsData& G, float& lam0, f2& lam12, float& c
 
 // T[i].p.y, T[i].q = this lane's three contact rows (hub / plate wrench per unit impulse); X[i].p.y, X[i].q = B = Phi T
 struct PgsState { PgsData G; float lam0; f2 lam12; float c0; f2 c12; float m0, m1, m2, m3; };
-LM_DEV void pgs_setup(PgsState& S, int limb, float mu, float bn, const float vf[3], const float Wl[6], const R4 T[6], const R4 X[6]) {
+#ifndef LM_H3_XBLOCKS
+#define LM_H3_XBLOCKS 0
+#endif
+struct Stash;
+#if defined(LM_HELPER_WAVE) && LM_HELPER_WAVE >= 2
+LM_DEV void xblocks_fetch(const Stash* Hd, XRaw& R0, XRaw& R1, XRaw& R2, XRaw& R3);      // (with the helpers, below)
+#endif
+// a value computed here and now: the optimiser neither sinks its computation behind a later barrier nor sees through it
+LM_DEV void pin_here(float& x) { asm volatile("" : "+v"(x)); }
+LM_DEV void pin_here(f2& x) { asm volatile("" : "+v"(x)); }
+// XB (the first pass of wavefront 0 of k_step_h3, LM_H3_XBLOCKS): the four raw cross blocks are the helper wavefronts', fetched behind barrier B3
+template <int XB = 0>
+LM_DEV void pgs_setup(PgsState& S, int limb, float mu, float bn, const float vf[3], const float Wl[6], const R4 T[6], const R4 X[6], const Stash* Hd = nullptr) {
   PgsData& G = S.G; float Wf[6];
   // full own block = limb-local part + hub/plate part T_r^T Phi T_s
   {
@@ -328,13 +351,27 @@ LM_DEV void pgs_setup(PgsState& S, int limb, float mu, float bn, const float vf[
   }
   // friction impulses are carried as lam_t / mu (bound = the normal impulse); mu = 0 pins them at zero
   const float imu = mu > 0.f ? 1.0f / mu : 0.f;
-  const float nrW0 = -1.0f / Wf[0]; G.W0t = mk2(Wf[1], Wf[2]); G.nrWt = mk2(-imu / Wf[3], -imu / Wf[5]);
+  float nrW0 = -1.0f / Wf[0]; G.W0t = mk2(Wf[1], Wf[2]); G.nrWt = mk2(-imu / Wf[3], -imu / Wf[5]);
+#if defined(LM_HELPER_WAVE) && LM_HELPER_WAVE >= 2
+  if (XB) {
+    // all that is this wavefront's own stands in front of B3 (left to the optimiser, the own block is sunk behind the barrier, to its first use);
+    // behind it: the reads, the selects and the scaling
+    S.c0 = (vf[0] + bn) * nrW0; S.c12 = mk2(vf[1], vf[2]);
+    pin_here(Wf[0]); pin_here(Wf[1]); pin_here(Wf[2]); pin_here(Wf[3]); pin_here(Wf[4]); pin_here(Wf[5]);
+    pin_here(nrW0); pin_here(G.nrWt); pin_here(S.c0); pin_here(S.c12);
+    XRaw R0, R1, R2, R3; xblocks_fetch(Hd, R0, R1, R2, R3);
+    pgs_cross_select<0>(limb, R0, Wf, G.X0[0], G.X12[0]); pgs_cross_select<1>(limb, R1, Wf, G.X0[1], G.X12[1]);
+    pgs_cross_select<2>(limb, R2, Wf, G.X0[2], G.X12[2]); pgs_cross_select<3>(limb, R3, Wf, G.X0[3], G.X12[3]);
+  } else
+#endif
+  {
   pgs_cross_blocks<0>(limb, T, X, Wf, G.X0[0], G.X12[0]); pgs_cross_blocks<1>(limb, T, X, Wf, G.X0[1], G.X12[1]);
   pgs_cross_blocks<2>(limb, T, X, Wf, G.X0[2], G.X12[2]); pgs_cross_blocks<3>(limb, T, X, Wf, G.X0[3], G.X12[3]);
+  }
 #pragma unroll
   for (int k = 0; k < 4; k++) { G.X0[k][0] *= nrW0; G.X0[k][1] *= mu * nrW0; G.X0[k][2] *= mu * nrW0; G.X12[k][1] = sp2(mu) * G.X12[k][1]; G.X12[k][2] = sp2(mu) * G.X12[k][2]; }
   S.lam0 = 0.f; S.lam12 = sp2(0.f);
-  S.c0 = (vf[0] + bn) * nrW0; S.c12 = mk2(vf[1], vf[2]);
+  if (!XB) { S.c0 = (vf[0] + bn) * nrW0; S.c12 = mk2(vf[1], vf[2]); }
   S.m0 = limb == 0 ? 1.f : 0.f; S.m1 = limb == 1 ? 1.f : 0.f; S.m2 = limb == 2 ? 1.f : 0.f; S.m3 = limb == 3 ? 1.f : 0.f;
 }
 // sweeps it0 (even) ... it1 - 1.  Sweeps alternate direction (contacts 0,1,2,3 then 3,2,1,0): no limb is systematically relaxed first,
@@ -399,8 +436,19 @@ LM_DEV void integrate_free(FreeBody& F, const M3& R, float dt) {
 // the last word, and writes stash slots 7-15 themselves.  The task-layer state that wavefront 1 fetches during the last sub-step
 // (helper_task_state, lm_step.h) has five slots of its own, TASK_SLOT: a second pass of that sub-step still reads slots 0-18 and HAND_OUT
 #if LM_HELPER_WAVE >= 2
-#define STASH_SLOTS 34
 #define TASK_SLOT 29          // 5 slots, wavefront 1 -> wavefront 0: succ, consec, greset, reset | progress, episode, lact | lact, lqd | ltip, goal | goal
+#if LM_H3_XBLOCKS
+// The cross blocks of the contact operator on the helpers (helper_xblocks).  Hand-in, 10 slots, wavefront 0 -> helpers in front of the second
+// barrier: K0 K1 K2 | the factor's d | its strictly lower L.  Its first five slots are TASK_SLOT's: the helpers have read them when they pass B3,
+// wavefront 1 writes the task-layer state behind its last B3, and no second pass reads either.  Hand-back, 5 slots per helper, read by
+// wavefront 0 behind B3: two raw blocks of 9 floats, wavefront 2's (contacts 0, 1) first
+#define STASH_SLOTS 49
+#define XB_IN_A TASK_SLOT     // 5 slots: K0 | K0, K1 | K1 | K2 | K2, d0, d1
+#define XB_IN_B 34            // 5 slots: d2..d5 | L10 L20 L21 L30 | L31 L32 L40 L41 | L42 L43 L50 L51 | L52 L53 L54
+#define XB_OUT 39             // 2 x 5 slots: a00, a0t, c0.x | c0.y, c1, c2.x | c2.y, a00', a0t' | c0', c1' | c2'
+#else
+#define STASH_SLOTS 34
+#endif
 #else
 #define STASH_SLOTS 29
 #endif
@@ -573,6 +621,13 @@ LM_DEV SI plate_inertia_env(const lm_params* __restrict__ P, float m, float s) {
 // wavefront 0 has more work before the barrier than the helper has and does not wait there.
 // HW 2 (the first pass of wavefront 0 of k_step_h3): as HW 1, and Jq, the hub rows PB[i].p.y / PB[i].q and bn are not in I / bn either; the pass
 // reads them behind the same barrier from stash slots 7-15, where the terms helper (helper_wave_terms) has written them.
+// Row I of the pass's four-vector elimination, on the names of the function it stands in (cp, j12, PB, K0..K2, T, X); BIAS: what the hub solve
+// takes for the bias column.  A macro, so that substep_pass and the helpers of k_step_h3 (helper_xblocks) compile the same lines
+#define LM_PROW(I, BIAS) { \
+      const f2 k0 = sp2(comp<I>(K0)), k1 = sp2(comp<I>(K1)), k2 = sp2(comp<I>(K2)); \
+      T[I].p = fma_(cp[2], k2, fma_(cp[1], k1, fma_(cp[0], k0, PB[I].p))); \
+      T[I].q = fma_(-j12[2], k2, fma_(-j12[1], k1, fma_(-j12[0], k0, PB[I].q))); \
+      X[I].p = mk2(BIAS, T[I].p.y); X[I].q = T[I].q; }
 template <int MODE, int VAR, int DR, int CF, int HW = 0>
 LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBody& F, const PassTerms& I, float dt, float kd, const float cjv[3],
                          const bool sat[3], const float tsat[3], const float tgt[3], const float qd[3], float bn, float mu_dr,
@@ -624,8 +679,20 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
         A[I][2 * jp + 1] = quad_sum(v.y); } }
     LM_AROW(0) LM_AROW(1) LM_AROW(2) LM_AROW(3) LM_AROW(4) LM_AROW(5)
 #undef LM_AROW
+    Chol6 Ch;
 #ifdef LM_HELPER_WAVE
     if (HW) {
+#if LM_HELPER_WAVE >= 2 && LM_H3_XBLOCKS
+      if (HW == 2) {
+        // k_step_h3: the factor in front of the barrier (its input is this wavefront's own), and what the helpers need for the cross blocks
+        // (helper_xblocks) with it: whole rounded results that the lines below only use as operands
+        chol6(A, Ch);
+        put2(*Hd, XB_IN_A, K0.a, K0.b); put2(*Hd, XB_IN_A + 1, K0.c, K1.a); put2(*Hd, XB_IN_A + 2, K1.b, K1.c); put2(*Hd, XB_IN_A + 3, K2.a, K2.b);
+        Hd->put(XB_IN_A + 4, K2.c.x, K2.c.y, Ch.d[0], Ch.d[1]); Hd->put(XB_IN_B, Ch.d[2], Ch.d[3], Ch.d[4], Ch.d[5]);
+        Hd->put(XB_IN_B + 1, Ch.L[1][0], Ch.L[2][0], Ch.L[2][1], Ch.L[3][0]); Hd->put(XB_IN_B + 2, Ch.L[3][1], Ch.L[3][2], Ch.L[4][0], Ch.L[4][1]);
+        Hd->put(XB_IN_B + 3, Ch.L[4][2], Ch.L[4][3], Ch.L[5][0], Ch.L[5][1]); Hd->put(XB_IN_B + 4, Ch.L[5][2], Ch.L[5][3], Ch.L[5][4], 0.f);
+      }
+#endif
       hw_barrier();      // the helper's second barrier of the sub-step: its bias terms are in LDS
       const float4 b0 = Hd->get(HAND_OUT), b1 = Hd->get(HAND_OUT + 1), b2 = Hd->get(HAND_OUT + 2);
       const float fcs[6] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y}, hqh[3] = {b1.z, b1.w, b2.x};
@@ -653,16 +720,11 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
       }
     }
 #endif
-    Chol6 Ch; chol6(A, Ch);
+    if (!(HW == 2 && LM_H3_XBLOCKS)) chol6(A, Ch);
     // (bias | row 0) and (row 1 | row 2) with the limb's joints eliminated:  P = PB + coefficient x K,  T_r = Jb_r - K Jq_r^T
     const f2 cp[3] = {mk2(r[0], -Jq[0][0]), mk2(r[1], -Jq[0][1]), mk2(r[2], -Jq[0][2])};
-#define LM_PROW(I) { \
-      const f2 k0 = sp2(comp<I>(K0)), k1 = sp2(comp<I>(K1)), k2 = sp2(comp<I>(K2)); \
-      T[I].p = fma_(cp[2], k2, fma_(cp[1], k1, fma_(cp[0], k0, PB[I].p))); \
-      T[I].q = fma_(-j12[2], k2, fma_(-j12[1], k1, fma_(-j12[0], k0, PB[I].q))); \
-      X[I].p = mk2(-quad_sum(T[I].p.x), T[I].p.y); X[I].q = T[I].q; }
-    LM_PROW(0) LM_PROW(1) LM_PROW(2) LM_PROW(3) LM_PROW(4) LM_PROW(5)
-#undef LM_PROW
+    LM_PROW(0, -quad_sum(T[0].p.x)) LM_PROW(1, -quad_sum(T[1].p.x)) LM_PROW(2, -quad_sum(T[2].p.x))
+    LM_PROW(3, -quad_sum(T[3].p.x)) LM_PROW(4, -quad_sum(T[4].p.x)) LM_PROW(5, -quad_sum(T[5].p.x))
     chol6_solve4(Ch, X);          // X = (a0 | B0), (B1 | B2): hub acceleration and Phi T without forming Phi
     float t0 = r[0], t1 = r[1], t2 = r[2];
 #define LM_TROW(I) { const float a = X[I].p.x; t0 = fmaf(-comp<I>(Fq0), a, t0); t1 = fmaf(-comp<I>(Fq1), a, t1); t2 = fmaf(-comp<I>(Fq2), a, t2); }
@@ -724,8 +786,10 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
   }
   float lam[3], w[6];
   LM_STAMP(3);
-  PgsState S; pgs_setup(S, limb, DR ? mu_dr : P->mu, HW == 2 ? bnh : bn, vf, Wl, T, X);
-  pgs_sweeps(S, 0, P->pgs_iters);
+  constexpr int XB = (HW == 2 && LM_H3_XBLOCKS) ? 1 : 0;
+  const int iters = XB ? P->pgs_iters : 0;      // (XB: read in front of barrier B3, not behind it with the sweeps waiting for it)
+  PgsState S; pgs_setup<XB>(S, limb, DR ? mu_dr : P->mu, HW == 2 ? bnh : bn, vf, Wl, T, X, Hd);
+  pgs_sweeps(S, 0, XB ? iters : P->pgs_iters);
   pgs_finish(S, DR ? mu_dr : P->mu, X, lam, w);
   if (CF) { lamc[0] = lam[0]; lamc[1] = lam[1]; lamc[2] = lam[2]; }
   un = sv(v3(v0f[0] + w[0], v0f[1] + w[1], v0f[2] + w[2]), v3(v0f[3] + w[3], v0f[4] + w[4], v0f[5] + w[5]));
@@ -740,6 +804,58 @@ LM_DEV void substep_pass(const lm_params* __restrict__ P, int limb, const FreeBo
 }
 
 #ifdef LM_HELPER_WAVE
+#if LM_HELPER_WAVE >= 2
+// wavefront 0 of k_step_h3 (pgs_setup, XB): barrier B3, then the four raw cross blocks from the helpers' hand-back slots
+LM_DEV void xblocks_fetch(const Stash* Hd, XRaw& R0, XRaw& R1, XRaw& R2, XRaw& R3) {
+#if LM_H3_XBLOCKS
+  hw_barrier();      // B3: the cross blocks are in LDS
+  const float4 a0 = Hd->get(XB_OUT), a1 = Hd->get(XB_OUT + 1), a2 = Hd->get(XB_OUT + 2), a3 = Hd->get(XB_OUT + 3), a4 = Hd->get(XB_OUT + 4);
+  const float4 b0 = Hd->get(XB_OUT + 5), b1 = Hd->get(XB_OUT + 6), b2 = Hd->get(XB_OUT + 7), b3 = Hd->get(XB_OUT + 8), b4 = Hd->get(XB_OUT + 9);
+  R0.a00 = a0.x; R0.a0t = mk2(a0.y, a0.z); R0.c0 = mk2(a0.w, a1.x); R0.c1 = mk2(a1.y, a1.z); R0.c2 = mk2(a1.w, a2.x);
+  R1.a00 = a2.y; R1.a0t = mk2(a2.z, a2.w); R1.c0 = mk2(a3.x, a3.y); R1.c1 = mk2(a3.z, a3.w); R1.c2 = mk2(a4.x, a4.y);
+  R2.a00 = b0.x; R2.a0t = mk2(b0.y, b0.z); R2.c0 = mk2(b0.w, b1.x); R2.c1 = mk2(b1.y, b1.z); R2.c2 = mk2(b1.w, b2.x);
+  R3.a00 = b2.y; R3.a0t = mk2(b2.z, b2.w); R3.c0 = mk2(b3.x, b3.y); R3.c1 = mk2(b3.z, b3.w); R3.c2 = mk2(b4.x, b4.y);
+#endif
+}
+#if LM_H3_XBLOCKS
+// The cross blocks of the contact operator on the two helpers of k_step_h3 (LM_H3_XBLOCKS).  Behind the second barrier of a
+// sub-step wavefront 0 still eliminates, solves and builds its own block alone, about 700 instructions before the first PGS turn, while the
+// helpers wait for the next sub-step.  Here each helper takes K and the hub factor (wavefront 0 factors in front of that barrier and publishes
+// both, XB_IN_*) and the contact rows (slots 7-15, the terms helper's), runs the pass's elimination (LM_PROW) and hub solve (chol6_solve4) on
+// the three contact columns - the bias column, the .p.x half, is zero here and is wavefront 0's alone - and then two of the four raw blocks
+// (pgs_cross_raw<KA>, <KB>) into its five hand-back slots, and passes barrier B3; wavefront 0 passes B3 where pgs_setup needs the blocks.
+// Same bits as k_step: every line up to the blocks is an explicit fma on rounded operands (nothing for the compiler to contract another way),
+// the two halves of a packed instruction do not see each other, and the blocks cross the cut raw, before the own-block select and the scaling.
+// B3 follows the discipline written above helper_wave: once per sub-step in straight-line code in all three wavefronts; the second pass (HW 0)
+// computes its own blocks and has no barrier.  Hazards: wavefront 0 writes the hand-in slots behind the sub-step's first barrier, the helpers
+// read them between the second and B3; the helpers write the hand-back slots behind the second barrier, wavefront 0 reads them behind B3 and
+// has used them before the next sub-step's first.
+template <int KA, int KB>
+LM_DEV void helper_xblocks(const Stash& St, int out) {
+  const float4 i0 = St.get(XB_IN_A), i1 = St.get(XB_IN_A + 1), i2 = St.get(XB_IN_A + 2), i3 = St.get(XB_IN_A + 3), i4 = St.get(XB_IN_A + 4);
+  const float4 i5 = St.get(XB_IN_B), i6 = St.get(XB_IN_B + 1), i7 = St.get(XB_IN_B + 2), i8 = St.get(XB_IN_B + 3), i9 = St.get(XB_IN_B + 4);
+  const float4 t7 = St.get(7), t8 = St.get(8), t9 = St.get(9);
+  const float4 g0 = St.get(10), g1 = St.get(11), g2 = St.get(12), g3 = St.get(13), g4 = St.get(14), g5 = St.get(15);
+  S6 K0, K1, K2;
+  K0.a = mk2(i0.x, i0.y); K0.b = mk2(i0.z, i0.w); K0.c = mk2(i1.x, i1.y); K1.a = mk2(i1.z, i1.w); K1.b = mk2(i2.x, i2.y); K1.c = mk2(i2.z, i2.w);
+  K2.a = mk2(i3.x, i3.y); K2.b = mk2(i3.z, i3.w); K2.c = mk2(i4.x, i4.y);
+  Chol6 Ch;      // (the strictly lower triangle and d: all the solve reads)
+  Ch.d[0] = i4.z; Ch.d[1] = i4.w; Ch.d[2] = i5.x; Ch.d[3] = i5.y; Ch.d[4] = i5.z; Ch.d[5] = i5.w;
+  Ch.L[1][0] = i6.x; Ch.L[2][0] = i6.y; Ch.L[2][1] = i6.z; Ch.L[3][0] = i6.w; Ch.L[3][1] = i7.x; Ch.L[3][2] = i7.y; Ch.L[4][0] = i7.z; Ch.L[4][1] = i7.w;
+  Ch.L[4][2] = i8.x; Ch.L[4][3] = i8.y; Ch.L[5][0] = i8.z; Ch.L[5][1] = i8.w; Ch.L[5][2] = i9.x; Ch.L[5][3] = i9.y; Ch.L[5][4] = i9.z;
+  const f2 cp[3] = {mk2(0.f, -t7.y), mk2(0.f, -t7.z), mk2(0.f, -t7.w)};
+  const f2 j12[3] = {mk2(t8.x, t8.y), mk2(t8.z, t8.w), mk2(t9.x, t9.y)};
+  R4 PB[6], T[6], X[6];
+  PB[0].p = mk2(0.f, g0.y); PB[1].p = mk2(0.f, g0.w); PB[2].p = mk2(0.f, g1.y); PB[3].p = mk2(0.f, g1.w); PB[4].p = mk2(0.f, g2.y); PB[5].p = mk2(0.f, g2.w);
+  PB[0].q = mk2(g3.x, g3.y); PB[1].q = mk2(g3.z, g3.w); PB[2].q = mk2(g4.x, g4.y); PB[3].q = mk2(g4.z, g4.w); PB[4].q = mk2(g5.x, g5.y); PB[5].q = mk2(g5.z, g5.w);
+  LM_PROW(0, 0.f) LM_PROW(1, 0.f) LM_PROW(2, 0.f) LM_PROW(3, 0.f) LM_PROW(4, 0.f) LM_PROW(5, 0.f)
+  chol6_solve4(Ch, X);
+  XRaw A, B; pgs_cross_raw<KA>(T, X, A); pgs_cross_raw<KB>(T, X, B);
+  St.put(out, A.a00, A.a0t.x, A.a0t.y, A.c0.x); St.put(out + 1, A.c0.y, A.c1.x, A.c1.y, A.c2.x); St.put(out + 2, A.c2.y, B.a00, B.a0t.x, B.a0t.y);
+  St.put(out + 3, B.c0.x, B.c0.y, B.c1.x, B.c1.y); St.put(out + 4, B.c2.x, B.c2.y, 0.f, 0.f);
+}
+#endif
+#endif
 // The helper wavefront of k_step_h2 (threads 64-127; lane l serves lane l of wavefront 0).  Per locomotion sub-step it recomputes the limb
 // kinematics and the placed inertias from the joint state wavefront 0 published, runs the bias chain of limb_dynamics and the hub's own bias
 // term (limb 0 carries the hub, as in substep) and leaves the limb's bias wrench and joint-space bias for wavefront 0: about 900 instructions
@@ -782,6 +898,10 @@ LM_DEV void helper_wave(const lm_params* __restrict__ P, const float* sTab, floa
     }
     St.put(HAND_OUT, D.fcs.w.x, D.fcs.w.y, D.fcs.w.z, D.fcs.v.x); St.put(HAND_OUT + 1, D.fcs.v.y, D.fcs.v.z, D.hq[0], D.hq[1]); St.put(HAND_OUT + 2, D.hq[2], 0.f, 0.f, 0.f);
     hw_barrier();      // the bias terms are in LDS
+#if LM_HELPER_WAVE >= 2 && LM_H3_XBLOCKS
+    helper_xblocks<2, 3>(St, XB_OUT + 5);
+    hw_barrier();      // B3: the cross blocks are in LDS
+#endif
   }
 }
 #if LM_HELPER_WAVE >= 2
@@ -823,6 +943,10 @@ LM_DEV void helper_wave_terms(const lm_params* __restrict__ P, const float* sTab
     St.put(10, 0.f, n0.x, 0.f, n0.y); St.put(11, 0.f, n0.z, 0.f, C0.x); St.put(12, 0.f, C0.y, 0.f, C0.z);
     St.put(13, n1.x, n2.x, n1.y, n2.y); St.put(14, n1.z, n2.z, C1.x, C2.x); St.put(15, C1.y, C2.y, C1.z, C2.z);
     hw_barrier();      // the contact terms are in LDS
+#if LM_H3_XBLOCKS
+    helper_xblocks<0, 1>(St, XB_OUT);
+    hw_barrier();      // B3: the cross blocks are in LDS
+#endif
   }
 }
 #endif

@@ -10,8 +10,17 @@
 // wavefront 0 still factors and sweeps, fetches the task-layer state (19 words per lane; in a resetting wavefront the goal draw and the reset
 // values) into five stash slots of its own and ends behind one more barrier, R1, behind which wavefront 0 reads them (helper_task_state, lm_step.h).
 // Barriers of the tail, per wavefront: 0: R1 - output barrier; 1: R1, ends; 2: R1 - output barrier.
+//
+// -DLM_H3_XBLOCKS (1 by default; 0 builds the kernel without it and without its barrier, for A/B): behind the second barrier of every sub-step the
+// two helpers, which would otherwise wait for the next sub-step, run the pass's elimination and hub solve on the three contact columns and two
+// of the four raw cross blocks of the contact operator each, from K and the hub factor that wavefront 0 publishes in front of that barrier, and
+// hand the blocks back behind a third barrier of the sub-step, B3 (helper_xblocks, lm_dynamics.h).  Barriers of a sub-step, in all three
+// wavefronts: first - second - B3; a second pass has none.
 #ifndef LM_HELPER_WAVE
 #define LM_HELPER_WAVE 2
+#endif
+#ifndef LM_H3_XBLOCKS
+#define LM_H3_XBLOCKS 1
 #endif
 #ifndef LM_H3_OUT_HELPER
 #define LM_H3_OUT_HELPER 1
