@@ -290,6 +290,58 @@ int lm_adam_clip_step(float* params, const float* grad, float* exp_avg, float* e
  * Writes state[LM_OPTIM_LR] and state[LM_OPTIM_KL] = kl_mean.  Returns as above (count < 1 is LM_EINVAL). */
 int lm_kl_adaptive_lr(double* state, const float* kl, int count, double threshold, double lr_min, double lr_max, void* stream);
 
+/* ---- the rest of a PPO iteration (csrc/lm_prepare.hip): the parameter pack of the forward kernels from the flat block the optimiser steps,
+ * and the batch preparation of train/ppo.py PPO.update (both running scalers, the normalisation of observations, returns, old values and
+ * advantages).  With them an iteration is a fixed sequence of launches that never waits for the host.  Every entry point validates on the host
+ * before any launch - LM_EINVAL (-1) with an lm_last_error text for a null pointer, a size outside its set, a misaligned block, a workspace that
+ * is too small, or buffers that are not memory of the calling thread's current device; nothing is launched and nothing written - and none of
+ * them synchronises the device or allocates.  -2 for a launch failure.
+ *
+ * Scaler state: device double [2 C + 1] = mean (C) | var (C) | count, 8-byte aligned: the state of train/ppo.py RunningStandardScaler
+ * (initially 0, 1, 1).  The value scaler's has C = 1.
+ *
+ * lm_mlp_pack_params: ONE launch.  flat = the block of lm_mlp_ppo_grad (num_obs 64 or 88); packed = the block of lm_mlp_forward_obs
+ * (lm_mlp_param_count_obs(num_obs) words, 16-byte aligned), bit for bit what policies/mlp_model.py pack_mlp_params builds from the same
+ * weights: hi / lo fp16 halves rounded to nearest even in the two K orders, 88 padded to 96, the head block with row 12 the value head and rows
+ * 13..15 zero, biases, then the scaler rows  mean = float(state mean) | istd = 1 / (sqrt(float(var)) + float(eps)), every step the correctly
+ * rounded fp32 result | clip.  scaler_state == NULL: mean 0, istd 1 and 3.0e38 in the clip word (eps and clip are then not read).
+ * lm_gnn_pack_params: the same for the block of lm_gnn_forward (num_obs must be 64): the flat block of lm_gnn_ppo_grad without log_std,
+ * followed by the mean row, the istd row and the clip word.
+ * status: device int32.  The kernel ORs bits into it and never clears it (the caller zeroes it once): LM_PACK_NONFINITE a weight that is not
+ * finite, LM_PACK_RANGE a finite weight with |w| >= 6.0e4 - the two conditions the torch packers raise on, over the tensors they check (the MLP's
+ * four weight matrices; all of the GNN's block).  The content of packed after a flagged call is unspecified. */
+enum { LM_PACK_NONFINITE = 1, LM_PACK_RANGE = 2 };
+int lm_mlp_pack_params(const float* flat, int num_obs, const double* scaler_state, double eps, double clip, float* packed, int32_t* status,
+                       void* stream);
+int lm_gnn_pack_params(const float* flat, int num_obs, const double* scaler_state, double eps, double clip, float* packed, int32_t* status,
+                       void* stream);
+
+/* Batch statistics, ONE launch: obs [B][C] (16-byte aligned), ret [B], adv [B] (device fp32; C 64 or 88; B >= 2, because the unbiased deviation
+ * of one sample is not a number) ->
+ *   sums, device double [lm_ppo_batch_sums_len(C) = 2 C + 5]:  S obs_c (C) | S obs_c^2 (C) | S ret | S ret^2 | S adv | S adv^2 | B
+ * All accumulation is in double in an order fixed by (B, C): per-workgroup partial sums in the workspace, then one pass over them in workgroup
+ * order by the workgroup that finishes last (an integer ticket; no floating-point atomics).  Two calls write the same bits.
+ * workspace: device memory, 16-byte aligned, at least lm_ppo_batch_stats_workspace(B, C) bytes.  Its first word is the ticket counter: it must
+ * be 0 before the first call (a zeroed allocation) and every call leaves it 0; the rest may hold anything.  One workspace serves one stream. */
+int lm_ppo_batch_sums_len(int C);
+long long lm_ppo_batch_stats_workspace(int B, int C);
+int lm_ppo_batch_stats(const float* obs, const float* ret, const float* adv, int B, int C, double* sums, void* workspace, long long workspace_bytes,
+                       void* stream);
+
+/* Merge and apply, TWO launches (one workgroup that writes the two states, then the apply, which only reads them).
+ * Merge: n = sums[2 C + 4] samples into obs_state (C features; skipped when freeze_obs != 0) and val_state (1 feature, from S ret), with the
+ * formula and the operation order of RunningStandardScaler.update, in double, no contraction:
+ *   bmean = s / n;  bvar = max(ss / n - bmean bmean, 0) n / max(n - 1, 1);  delta = bmean - mean;  tot = count + n
+ *   m2 = var count + bvar n + delta delta count n / tot;  mean = mean + delta n / tot;  var = m2 / tot;  count = tot
+ * Apply, from the merged states, evaluated in double and rounded to fp32 once:
+ *   obs_n = clamp((obs - mean) / (sqrt(var) + eps), -clip, +clip);  ret_n, old_val_n: the same with the value scaler
+ *   adv_n = (adv - S adv / n) / (sqrt(max((S adv^2 - (S adv)^2 / n) / (n - 1), 0)) + 1e-8)          (the unbiased deviation, from the sums)
+ * sums is read only, so a multi-rank caller can all-reduce it between lm_ppo_batch_stats and this call.  obs and obs_n 16-byte aligned;
+ * inputs and outputs must not overlap. */
+int lm_ppo_batch_apply(const float* obs, const float* ret, const float* old_val, const float* adv, int B, int C, const double* sums,
+                       double* obs_state, double* val_state, int freeze_obs, double eps, double clip, float* obs_n, float* ret_n,
+                       float* old_val_n, float* adv_n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,7 +72,8 @@ EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass
            "lm_rollout_set_trajectory_record", "lm_trajectory_update",
            "lm_mlp_grad_param_count", "lm_mlp_ppo_grad", "lm_mlp_ppo_grad_workspace", "lm_mlp_ppo_grad_geometry", "lm_gae",
            "lm_gnn_grad_param_count", "lm_gnn_ppo_grad", "lm_gnn_ppo_grad_workspace", "lm_gnn_ppo_grad_geometry",
-           "lm_optim_state_len", "lm_optim_state_init", "lm_adam_clip_step", "lm_kl_adaptive_lr"]
+           "lm_optim_state_len", "lm_optim_state_init", "lm_adam_clip_step", "lm_kl_adaptive_lr",
+           "lm_mlp_pack_params", "lm_gnn_pack_params", "lm_ppo_batch_sums_len", "lm_ppo_batch_stats_workspace", "lm_ppo_batch_stats", "lm_ppo_batch_apply"]
 
 # rows of the SoA float state
 ROW = dict(base_pos=0, base_quat=3, base_lin=7, base_ang=10, q=13, qd=25, plate_pos=37, plate_quat=40, plate_lin=44,
@@ -245,7 +246,7 @@ def hipcc_command(extra, out):
     # LDS stores) needs no v_accvgpr_read per element (504 of them in k_gnn_forward)
     return [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
             "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_h2.hip"), os.path.join(_CSRC, "lm_engine_h3.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"), os.path.join(_CSRC, "lm_engine_tr.hip"), os.path.join(_CSRC, "lm_engine_hp.hip"),
-            os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), os.path.join(_CSRC, "lm_gnn_ppo.hip"), os.path.join(_CSRC, "lm_optim.hip"), "-o", out]
+            os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), os.path.join(_CSRC, "lm_gnn_ppo.hip"), os.path.join(_CSRC, "lm_optim.hip"), os.path.join(_CSRC, "lm_prepare.hip"), "-o", out]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -322,6 +323,12 @@ def load_library() -> C.CDLL:
     lib.lm_optim_state_init.argtypes = [fp, C.c_double, C.c_double, vp]
     lib.lm_adam_clip_step.argtypes = [fp, fp, fp, fp, ip, fp, C.POINTER(LmOptimHyper), vp]
     lib.lm_kl_adaptive_lr.argtypes = [fp, fp, ip, C.c_double, C.c_double, C.c_double, vp]
+    lib.lm_mlp_pack_params.argtypes = [fp, ip, fp, C.c_double, C.c_double, fp, vp, vp]
+    lib.lm_gnn_pack_params.argtypes = [fp, ip, fp, C.c_double, C.c_double, fp, vp, vp]
+    lib.lm_ppo_batch_sums_len.argtypes = [ip]
+    lib.lm_ppo_batch_stats_workspace.argtypes = [ip, ip]; lib.lm_ppo_batch_stats_workspace.restype = C.c_longlong
+    lib.lm_ppo_batch_stats.argtypes = [fp, fp, fp, ip, ip, fp, vp, C.c_longlong, vp]
+    lib.lm_ppo_batch_apply.argtypes = [fp, fp, fp, fp, ip, ip, fp, fp, fp, ip, C.c_double, C.c_double, fp, fp, fp, fp, vp]
     lib.lm_last_error.restype = C.c_char_p
     lib.lm_version.restype = C.c_char_p
     _lib = lib

@@ -10,6 +10,8 @@ the gradients are all-reduced.  Rollouts use the matrix-core policy forward (csr
 fused loss-gradient kernels and the GAE kernel: PPO(hip_update=True) for the SharedMLP (csrc/lm_ppo.hip),
 PPO(gnn_hip_update=True) for the GraphPolicy (csrc/lm_gnn_ppo.hip).  With either of them, PPO(hip_optimizer=True) also runs the gradient-norm
 clip, Adam and the KL-adaptive rate on the device (csrc/lm_optim.hip): the epoch loop then holds no torch optimiser launch and no host wait.
+PPO(hip_prepare=True) moves the rest there too (csrc/lm_prepare.hip): the parameter pack of the rollout's forward kernel, both running scalers and
+the normalisation of the batch; with hip_optimizer as well, update(last_value, fetch=False) is a fixed sequence of launches with no host wait.
 """
 from __future__ import annotations
 
@@ -24,13 +26,26 @@ from .. import distributed as D
 
 
 class RunningStandardScaler:
-    """skrl.resources.preprocessors.torch.RunningStandardScaler: running mean/variance, (x-mean)/(sqrt(var)+eps), clip 5."""
+    """skrl.resources.preprocessors.torch.RunningStandardScaler: running mean/variance, (x-mean)/(sqrt(var)+eps), clip 5.
+    device_block=True: mean, var and count are views of ONE float64 block `state` = mean | var | count, which the kernels of csrc/lm_prepare.hip
+    read and update in place (update() and load_state_dict() then write through the views); everything else behaves the same."""
 
-    def __init__(self, size: int, device, epsilon: float = 1e-8, clip: float = 5.0):
-        self.mean = torch.zeros(size, device=device, dtype=torch.float64)
-        self.var = torch.ones(size, device=device, dtype=torch.float64)
-        self.count = torch.ones((), device=device, dtype=torch.float64)
+    def __init__(self, size: int, device, epsilon: float = 1e-8, clip: float = 5.0, device_block: bool = False):
+        self.state = None
+        if device_block:
+            self.state = torch.zeros(2 * size + 1, device=device, dtype=torch.float64); self.state[size:] = 1.0
+            self.mean, self.var, self.count = self.state[:size], self.state[size:2 * size], self.state[2 * size]
+        else:
+            self.mean = torch.zeros(size, device=device, dtype=torch.float64)
+            self.var = torch.ones(size, device=device, dtype=torch.float64)
+            self.count = torch.ones((), device=device, dtype=torch.float64)
         self.eps, self.clip = epsilon, clip
+
+    def _set(self, mean, var, count):
+        if self.state is None:
+            self.mean, self.var, self.count = mean, var, count
+        else:
+            self.mean.copy_(mean); self.var.copy_(var); self.count.copy_(count)
 
     def update(self, x: torch.Tensor):
         x = x.reshape(-1, self.mean.numel()).double()
@@ -41,7 +56,7 @@ class RunningStandardScaler:
         bmean = s / n; bvar = (ss / n - bmean * bmean).clamp_min(0) * n / (n - 1).clamp_min(1)
         delta = bmean - self.mean; tot = self.count + n
         m2 = self.var * self.count + bvar * n + delta * delta * self.count * n / tot
-        self.mean = self.mean + delta * n / tot; self.var = m2 / tot; self.count = tot
+        self._set(self.mean + delta * n / tot, m2 / tot, tot)
 
     def state_dict(self):
         return {"mean": self.mean.detach().cpu().clone(), "var": self.var.detach().cpu().clone(), "count": self.count.detach().cpu().clone()}
@@ -49,7 +64,7 @@ class RunningStandardScaler:
     def load_state_dict(self, sd):
         dev = self.mean.device
         assert tuple(sd["mean"].shape) == tuple(self.mean.shape), (tuple(sd["mean"].shape), tuple(self.mean.shape))
-        self.mean, self.var, self.count = (sd[k].to(dev, torch.float64).clone() for k in ("mean", "var", "count"))
+        self._set(*(sd[k].to(dev, torch.float64).clone() for k in ("mean", "var", "count")))
 
     def __call__(self, x: torch.Tensor, inverse: bool = False):
         mean, std = self.mean.float(), self.var.float().sqrt()
@@ -84,7 +99,12 @@ class PPO:
     def __init__(self, env, model, rollouts=48, learning_epochs=5, mini_batches=1, gamma=0.99, lam=0.95, lr=3e-4, kl_threshold=0.012,
                  grad_norm_clip=1.0, ratio_clip=0.2, value_clip=0.2, value_loss_scale=1.0, entropy_loss_scale=0.0, hip_inference=True,
                  fused_rollout=True, freeze_obs_scaler=False, max_lr=1e-2, min_log_std=None, hip_update=False, gnn_hip_update=False,
-                 hip_optimizer=False):
+                 hip_optimizer=False, hip_prepare=False):
+        """hip_prepare=True (with hip_update or gnn_hip_update, on a HIP device, one rank, a fused rollout): collect() packs the rollout's
+        parameter block with one launch from the flat block and the observation scaler's state block (no model.refresh, no blocking read), and
+        update() prepares the batch with the launches of csrc/lm_prepare.hip.  The packers' range check becomes a status word on the device: a
+        weight that is not finite or not below 6e4 raises their ValueError at the next fetch (the next update(fetch=True), i.e. the next logged
+        iteration of train(), or state_dict()), not at the collect() that met it."""
         self.env, self.model = env, model
         self.dev = next(model.parameters()).device
         self.phase_marks = None       # timing hook: see _mark
@@ -92,6 +112,16 @@ class PPO:
         if self.hip_optimizer and not (hip_update or gnn_hip_update):
             raise ValueError("hip_optimizer=True steps the flat parameter blocks of a fused update: pass hip_update=True (SharedMLP) or gnn_hip_update=True "
                              "(GraphPolicy) as well")
+        self.hip_prepare = bool(hip_prepare)
+        if self.hip_prepare:
+            if not (hip_update or gnn_hip_update):
+                raise ValueError("hip_prepare=True packs the rollout's parameters from the flat block of a fused update: pass hip_update=True (SharedMLP) or "
+                                 "gnn_hip_update=True (GraphPolicy) as well")
+            if self.dev.type != "cuda" or not torch.cuda.is_available():
+                raise ValueError(f"hip_prepare=True needs the model on a HIP device, not {self.dev} (the kernels have no CPU fallback)")
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise ValueError("hip_prepare=True runs on one rank: the all-reduce of the batch sums between lm_ppo_batch_stats and lm_ppo_batch_apply "
+                                 "is not built yet (world > 1)")
         self.hip_update = bool(hip_update)
         if self.hip_update:
             # no CPU fallback and no quiet autograd path, as in lib.Engine: say why and stop
@@ -131,12 +161,14 @@ class PPO:
             from ..policies.optim import optim_state
             self._m, self._v = torch.zeros_like(self._flat), torch.zeros_like(self._flat)
             self._ostate = optim_state(self.dev, lr, 0)
-            self._fetch = torch.zeros(self._ostate.numel() + 2, device=self.dev, dtype=torch.float64)
+            self._fetch = torch.zeros(self._ostate.numel() + 2 + int(self.hip_prepare), device=self.dev, dtype=torch.float64)      # + the pack status slot
+            if self.hip_prepare: self._fetch[:self._ostate.numel()].copy_(self._ostate)      # the fetch block mirrors the state block between updates
             self._stats_all, self.last_kls = None, None
         self.freeze_obs_scaler = freeze_obs_scaler          # diagnostics: identity observation scaler (mean 0, var 1)
         self.max_lr, self.min_log_std = max_lr, min_log_std  # diagnostics: cap of the KL-adaptive rate (skrl: 1e-2); floor of log_std (skrl: -20)
         self.n_obs = int(env.observation_space.shape[0])          # 88 for the custom-controller tasks
-        self.obs_scaler = RunningStandardScaler(self.n_obs, self.dev); self.val_scaler = RunningStandardScaler(1, self.dev)
+        self.obs_scaler = RunningStandardScaler(self.n_obs, self.dev, device_block=self.hip_prepare)
+        self.val_scaler = RunningStandardScaler(1, self.dev, device_block=self.hip_prepare)
         # MFMA forward kernels: MLP on the 64- and 88-wide observations, GNN on the 64-wide one
         self.hip = hip_inference and hasattr(model, "act_inference") and torch.cuda.is_available() and \
             (self.n_obs == 64 or (self.n_obs == 88 and type(model).__name__ == "SharedMLP"))
@@ -155,6 +187,15 @@ class PPO:
             ro = self.rollout
             self._ro_mode = "auto"      # one persistent kernel per rollout where the engine supports it and it pays, else the hipGraph replay
             self.b_obs, self.b_act, self.b_logp, self.b_rew = ro.obs[:self.T], ro.actions, ro.logp, ro.rewards
+        if self.hip_prepare:
+            if self.rollout is None:
+                raise ValueError("hip_prepare=True packs straight into a fused rollout's parameter block: it needs hip_inference and fused_rollout on an "
+                                 "engine task (env._task.make_rollout)")
+            # the pack status: an int32 the pack kernel ORs into.  With hip_optimizer it is the low half of the last slot of the fetch block, so that
+            # one copy brings the optimiser state, the losses and the status to the host
+            self._pstatus = self._fetch[-1:].view(torch.int32)[:1] if self.hip_optimizer else torch.zeros(1, device=self.dev, dtype=torch.int32)
+            self._kind = "gnn" if self.gnn_hip_update else "mlp"
+            self._sums = torch.zeros(2 * self.n_obs + 5, device=self.dev, dtype=torch.float64); self._prep = {}
 
     # ------------------------------------------------------------------ policy evaluation
     def _policy(self, obs_raw):
@@ -173,8 +214,13 @@ class PPO:
     def collect(self, obs_raw):
         if self.rollout is not None:
             ro = self.rollout
-            self.model.refresh(self.dev, self.obs_scaler.mean.float(), self.obs_scaler.var.float(), self.obs_scaler.eps, self.obs_scaler.clip)
-            self._packed.copy_(self.model._packed); self._log_std.copy_(self.model.log_std_parameter.detach())
+            if self.hip_prepare:      # one launch, flat block + scaler block -> the plan's parameter block; the range check goes to self._pstatus
+                from ..policies.prepare import pack_params
+                pack_params(self._kind, self._flat, self.n_obs, self._packed, self._pstatus, self.obs_scaler.state, self.obs_scaler.eps, self.obs_scaler.clip)
+                self._log_std.copy_(self.model.log_std_parameter.detach())
+            else:
+                self.model.refresh(self.dev, self.obs_scaler.mean.float(), self.obs_scaler.var.float(), self.obs_scaler.eps, self.obs_scaler.clip)
+                self._packed.copy_(self.model._packed); self._log_std.copy_(self.model.log_std_parameter.detach())
             ro.obs[0].copy_(obs_raw)
             ro.run(self._ro_mode)
             v = self.val_scaler(ro.values.reshape(-1, 1), inverse=True).reshape(self.T + 1, self.N)
@@ -195,7 +241,34 @@ class PPO:
         if self.phase_marks is not None:
             ev = torch.cuda.Event(enable_timing=True); ev.record(); self.phase_marks.append((phase, ev))
 
-    def update(self, last_value) -> Dict[str, float]:
+    def _check_pack_status(self, status: int):
+        if status:
+            from ..policies.prepare import pack_status_error
+            self._pstatus.zero_()
+            raise pack_status_error(int(status), self._kind)
+
+    def _prepare_batch(self, ret, adv):
+        """hip_prepare: lm_ppo_batch_stats + lm_ppo_batch_apply on the rollout's buffers (three launches): both scalers are merged in their state
+        blocks, and the normalised batch is written into buffers kept per batch size."""
+        from ..policies.prepare import batch_apply, batch_stats, batch_stats_workspace
+        obs = self.b_obs.reshape(-1, self.n_obs); ret, adv, old_val = ret.reshape(-1), adv.reshape(-1), self.b_val.reshape(-1)
+        B = obs.shape[0]
+        if B not in self._prep:
+            z = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
+            self._prep[B] = (batch_stats_workspace(B, self.n_obs, self.dev), (z(B, self.n_obs), z(B), z(B), z(B)))
+        ws, out = self._prep[B]
+        batch_stats(obs, ret, adv, self._sums, ws)
+        batch_apply(obs, ret, old_val, adv, self._sums, self.obs_scaler.state, self.val_scaler.state, self.freeze_obs_scaler, self.obs_scaler.eps,
+                    self.obs_scaler.clip, out)
+        return obs, ret, old_val, out
+
+    def update(self, last_value, fetch: bool = True):
+        """One PPO update on the rollout collect() has just filled.  Returns the statistics of the last mini-batch {kl, loss_pi, loss_v, lr}.
+        fetch=False (hip_prepare and hip_optimizer together only) returns None instead: the statistics, the optimiser state and the pack status stay
+        on the device, nothing is copied to the host and nothing waits for the device; self.lr and opt.param_groups are refreshed by the next
+        update that fetches, which is also where a bad weight seen by the pack kernel is reported."""
+        if not fetch and not (self.hip_prepare and self.hip_optimizer):
+            raise ValueError("update(fetch=False) leaves the statistics on the device: it needs hip_prepare=True and hip_optimizer=True")
         self._mark("start")
         if self._fused_update:      # one launch over the plan's own buffers (int64 dones), bit for bit compute_gae
             from ..policies.mlp_model import gae
@@ -204,14 +277,17 @@ class PPO:
         else:
             ret, adv = D.compute_gae(self.b_rew, self.b_val, self.b_done, last_value, self.gamma, self.lam)
         self._mark("gae")
-        g_ret, g_adv = D.all_gather_rollout(ret, adv)                 # RCCL all-gather over xGMI when world > 1
-        adv = (adv - g_adv.mean()) / (g_adv.std() + 1e-8)             # global advantage normalisation
-        obs, act = self.b_obs.reshape(-1, self.n_obs), self.b_act.reshape(-1, 12)
-        old_logp, old_val = self.b_logp.reshape(-1), self.b_val.reshape(-1)
-        ret, adv = ret.reshape(-1), adv.reshape(-1)
-        if not self.freeze_obs_scaler: self.obs_scaler.update(obs)
-        self.val_scaler.update(ret.unsqueeze(-1))      # preprocessors train on the first epoch's data
-        obs_n = self.obs_scaler(obs); ret_n = self.val_scaler(ret.unsqueeze(-1)).squeeze(-1); old_val_n = self.val_scaler(old_val.unsqueeze(-1)).squeeze(-1)
+        act, old_logp = self.b_act.reshape(-1, 12), self.b_logp.reshape(-1)
+        if self.hip_prepare:      # scalers, global advantage normalisation and the normalised batch: three launches, no torch
+            obs, ret, old_val, (obs_n, ret_n, old_val_n, adv) = self._prepare_batch(ret, adv)
+        else:
+            g_ret, g_adv = D.all_gather_rollout(ret, adv)                 # RCCL all-gather over xGMI when world > 1
+            adv = (adv - g_adv.mean()) / (g_adv.std() + 1e-8)             # global advantage normalisation
+            obs, old_val = self.b_obs.reshape(-1, self.n_obs), self.b_val.reshape(-1)
+            ret, adv = ret.reshape(-1), adv.reshape(-1)
+            if not self.freeze_obs_scaler: self.obs_scaler.update(obs)
+            self.val_scaler.update(ret.unsqueeze(-1))      # preprocessors train on the first epoch's data
+            obs_n = self.obs_scaler(obs); ret_n = self.val_scaler(ret.unsqueeze(-1)).squeeze(-1); old_val_n = self.val_scaler(old_val.unsqueeze(-1)).squeeze(-1)
         n = obs.shape[0]; stats = {}
         # what the mini-batches below are cut from (references, no copies): read by the tests of the HIP update
         self.last_batch = {"obs_n": obs_n, "act": act, "old_logp": old_logp, "old_val_n": old_val_n, "adv": adv, "ret_n": ret_n, "ret": ret}
@@ -220,10 +296,14 @@ class PPO:
             from ..policies.optim import STATE
             self._run_epochs(obs_n, act, old_logp, old_val_n, adv, ret_n)
             self._mark("epochs")
+            if not fetch:
+                return None
             h = self._fetch.cpu()                                                  # the update's one device-to-host copy
+            ns = self._ostate.numel()
+            if self.hip_prepare: self._check_pack_status(int(h[ns + 2:].view(torch.int32)[0]))
             self.lr = float(h[STATE["lr"]])
             for gp in self.opt.param_groups: gp["lr"] = self.lr
-            return {"kl": float(h[STATE["kl"]]), "loss_pi": float(h[-2]), "loss_v": float(h[-1]), "lr": self.lr}
+            return {"kl": float(h[STATE["kl"]]), "loss_pi": float(h[ns]), "loss_v": float(h[ns + 1]), "lr": self.lr}
         for epoch in range(self.epochs):
             perm = torch.randperm(n, device=self.dev) if self.mb > 1 else None
             kls = []
@@ -261,6 +341,7 @@ class PPO:
             for gp in self.opt.param_groups: gp["lr"] = self.lr
             stats = {"kl": kl, "loss_pi": float(loss_pi), "loss_v": float(loss_v), "lr": self.lr}
         self._mark("epochs")
+        if self.hip_prepare: self._check_pack_status(int(self._pstatus.cpu()[0]))
         return stats
 
     def _run_epochs(self, obs_n, act, old_logp, old_val_n, adv, ret_n):
@@ -291,7 +372,7 @@ class PPO:
                     self.last_kls[epoch].copy_(kls)
             kl_adaptive_lr(self._ostate, kls, self.kl_thr, 1e-6, self.max_lr)
         ns = self._ostate.numel()
-        self._fetch[:ns].copy_(self._ostate); self._fetch[ns:].copy_(self._stats_all[-1, :2])
+        self._fetch[:ns].copy_(self._ostate); self._fetch[ns:ns + 2].copy_(self._stats_all[-1, :2])
 
     def _hip_grad(self, obs_n, act, old_logp, old_val_n, adv, ret_n, stats=None):
         """lm_mlp_ppo_grad / lm_gnn_ppo_grad on one mini-batch: fills the flat gradient buffer (the parameters' .grad views) and `stats`
@@ -337,6 +418,14 @@ class PPO:
         self.opt.state.clear()
 
     def state_dict(self):
+        if self.hip_prepare and self.hip_optimizer:      # updates with fetch=False leave the rate on the device: one copy brings it and the pack status
+            from ..policies.optim import STATE
+            h = self._fetch.cpu()
+            self._check_pack_status(int(h[self._ostate.numel() + 2:].view(torch.int32)[0]))
+            self.lr = float(h[STATE["lr"]])
+            for gp in self.opt.param_groups: gp["lr"] = self.lr
+        elif self.hip_prepare:      # a checkpoint of weights the pack kernel has flagged is refused like an update's fetch
+            self._check_pack_status(int(self._pstatus.cpu()[0]))
         if self.hip_optimizer:      # the checkpoint is torch.optim.Adam's in every mode
             self._moments_to_opt()
             try:
@@ -359,6 +448,7 @@ class PPO:
         for gp in self.opt.param_groups: gp["lr"] = self.lr
         if self.hip_optimizer:
             self._moments_from_opt()
+            if self.hip_prepare: self._fetch[:self._ostate.numel()].copy_(self._ostate)      # the fetch block mirrors the state block between updates
 
     def save(self, path):
         torch.save(self.state_dict(), path)
@@ -370,8 +460,9 @@ class PPO:
         obs = self.env.reset()["obs"]; history = []; t0 = time.perf_counter()
         for it in range(timesteps // self.T):
             obs, last_value, extras = self.collect(obs)
-            st = self.update(last_value)
-            if it % log_every == 0 or it == timesteps // self.T - 1:
+            logged = it % log_every == 0 or it == timesteps // self.T - 1
+            st = self.update(last_value, fetch=logged) if (self.hip_prepare and self.hip_optimizer) else self.update(last_value)
+            if logged:
                 ex = D.global_extras(extras, self.N)
                 rec = {"iteration": it, "timesteps": (it + 1) * self.T, "wall_s": time.perf_counter() - t0, "mean_reward": float(self.b_rew.mean()),
                        "success_rate": float(ex["env/success_rate"]), "std": float(self.model.log_std_parameter.exp().mean()), **st}

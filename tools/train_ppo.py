@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Behavioural acceptance run: train the reference's PPO recipe on the engine and log the success-rate curve.
-    python tools/train_ppo.py --task QuadrupedPoseControl --num-envs 4096 --timesteps 4800 [--policy mlp|gnn] [--hip-update [--hip-optimizer]] [--out profiles/x.json] [--save agent.pt]
+    python tools/train_ppo.py --task QuadrupedPoseControl --num-envs 4096 --timesteps 4800 [--policy mlp|gnn] [--hip-update [--hip-optimizer] [--hip-prepare]] [--out profiles/x.json] [--save agent.pt]
 (multi-GPU: python -m torch.distributed.run --nproc-per-node N tools/train_ppo.py ...)"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,12 +26,16 @@ def main():
                     "(off by default: DESIGN.md 5.4 has the measured comparison)")
     ap.add_argument("--hip-optimizer", action="store_true", help="with --hip-update: the gradient-norm clip, Adam and the KL-adaptive rate on the device too (csrc/lm_optim.hip); "
                     "the epoch loop then never waits for the host (DESIGN.md 5.4)")
+    ap.add_argument("--hip-prepare", action="store_true", help="with --hip-update: the rollout's parameter pack, both running scalers and the batch normalisation on the device too "
+                    "(csrc/lm_prepare.hip); with --hip-optimizer as well, an iteration that is not logged never waits for the host (DESIGN.md 5.4)")
     ap.add_argument("--max-lr", type=float, default=1e-2, help="diagnostic: cap of the KL-adaptive learning rate (skrl default 1e-2)")
     ap.add_argument("--min-log-std", type=float, default=None, help="diagnostic: floor of the log-std parameter (skrl clips at -20 only)")
     ap.add_argument("--engine", action="append", default=[], metavar="KEY=VALUE", help="diagnostic: a sim.engine override of the task YAML, e.g. friction_scale=1.0")
     a = ap.parse_args()
     if a.hip_optimizer and not a.hip_update:
         ap.error("--hip-optimizer steps the flat parameter blocks of the fused update: it needs --hip-update")
+    if a.hip_prepare and not a.hip_update:
+        ap.error("--hip-prepare packs the rollout's parameters from the flat block of the fused update: it needs --hip-update")
     # LM_DIST_BACKEND=gloo: rehearsal of the multi-rank path on a box with fewer GPUs than ranks (ranks then share devices)
     backend = os.environ.get("LM_DIST_BACKEND")
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -57,10 +61,10 @@ def main():
         env.step = lambda act: _step(act[:, inv].contiguous())
         a.no_fused = True
     ppo = PPO(env, model, hip_inference=hip and not a.no_hip, fused_rollout=not a.no_fused, **({"kl_threshold": 0.0} if a.fixed_lr else {}), freeze_obs_scaler=a.no_obs_scaler, max_lr=a.max_lr, min_log_std=a.min_log_std,
-              hip_update=a.hip_update and a.policy != "gnn", gnn_hip_update=a.hip_update and a.policy == "gnn", hip_optimizer=a.hip_optimizer)
+              hip_update=a.hip_update and a.policy != "gnn", gnn_hip_update=a.hip_update and a.policy == "gnn", hip_optimizer=a.hip_optimizer, hip_prepare=a.hip_prepare)
     hist = ppo.train(a.timesteps, log_every=a.log_every, log=(lambda r: print(json.dumps(r), flush=True)) if rank == 0 else (lambda r: None))
     if rank == 0 and a.out:
-        json.dump({"task": a.task, "num_envs": a.num_envs, "world": world, "policy": a.policy, "hip_update": bool(a.hip_update), "hip_optimizer": bool(a.hip_optimizer), "seed": a.seed, "history": hist}, open(a.out, "w"), indent=1)
+        json.dump({"task": a.task, "num_envs": a.num_envs, "world": world, "policy": a.policy, "hip_update": bool(a.hip_update), "hip_optimizer": bool(a.hip_optimizer), "hip_prepare": bool(a.hip_prepare), "seed": a.seed, "history": hist}, open(a.out, "w"), indent=1)
     if rank == 0 and a.save:
         ppo.save(a.save)
     env.close()
