@@ -746,7 +746,9 @@ static StepArgs make_args(lm_engine* h, const float* actions, const float* goal_
   StepArgs A;
   A.params = h->d_params; A.table = h->d_table; A.state = h->d_state; A.cnt = h->d_cnt; A.actions = actions; A.goal_rand = goal_rand;
   A.W.obs_buf = h->d_obs; A.W.states_buf = h->d_states; A.W.rew_buf = h->d_rew; A.W.terms = h->d_terms; A.W.acc = h->d_acc;
-  A.W.stats = (char*)h->d_stats; A.W.extras = h->d_extras; A.W.out_extras = nullptr; A.W.split_block = h->split / ENVS_PER_WAVE; A.W.acc_rows = h->acc_rows;
+  // first block of the second task: rounded up, so that the ragged last block of a single-task engine (split = N) counts into the first-task
+  // window like every other one (the halves of joint_locomanipulation.py:846-859; a two-task split is a multiple of 16, lm_create)
+  A.W.stats = (char*)h->d_stats; A.W.extras = h->d_extras; A.W.out_extras = nullptr; A.W.split_block = (h->split + ENVS_PER_WAVE - 1) / ENVS_PER_WAVE; A.W.acc_rows = h->acc_rows;
   A.W.out_obs = out_obs; A.W.out_states = out_states; A.W.out_rew = out_rew; A.W.out_resets = out_resets;
   A.N = h->N; A.split = h->split; A.seed = h->seed; A.skip_reset = 0; A.nsub = -1; A.drc = h->d_drc; A.dr_phys = h->d_dr_phys; A.reset_dr = h->d_reset_dr; A.mass_dr = h->d_mass_dr;
   A.env_params = h->d_env_params; A.contact = h->contact_on ? h->d_contact : nullptr; A.actuator_dr = h->d_actuator_dr;

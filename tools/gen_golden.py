@@ -16,7 +16,8 @@ is the 7 quaternion helpers + unscale_transform of omni.isaac.core.utils.torch (
 source absent); their semantics are fixed by the call-site evidence listed in SURVEY 8(c)
 and they are unit-tested against scipy in tests/test_math_host.py.
 
-Run:  python -B tools/gen_golden.py
+Run:  python -B tools/gen_golden.py            (every file)
+      python -B tools/gen_golden.py branches   (tests/golden/task_branches.npz alone)
 """
 import importlib.abc
 import importlib.machinery
@@ -668,11 +669,96 @@ def gen_gnn(seed=11, B=40):
     return {k: v.numpy() for k, v in out.items()}
 
 
+# ----------------------------------------------------------------------------- the task layer at its branch points
+def build_branch_cases():
+    """The scenarios of tests/task_states.py the fixture covers (`all` layout, N = 16).  Built before the placeholders are installed and the
+    reference is put on sys.path: the builders are the project's own code (numpy and the oracle)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [root, os.path.join(root, "tests")]
+    import task_states as ts
+    from locomanipulationrl_amd.model.robot_model import load_model
+    rm = load_model("quadruped_robot_v2")
+    return ts, {name: ts.build(name, rm, ts.FIXTURE_N, 0, "all") for name in ts.FIXTURE_SCENARIOS}
+
+
+def gen_branches(ts, cases):
+    """The reference's own task classes on the branch-point scenarios: the class constants the scenarios move (fall_penalty,
+    rot_dist_decreasing_reward_scale, the thresholds, the episode and window lengths) are set on the task object, the task state and the counters
+    are the scenario's, the read-back is handed over through the same fakes as in gen_task, and the post-physics methods run unmodified.
+    pre_physics_step runs with the reset flags held back (a carried-in reset_buf is one of the cases), for current_actions and the
+    swing/extension integration."""
+    from utils.math import transform_vectors
+    out = {"names": np.array(list(cases))}
+    for name, case in cases.items():
+        ep = case.params; N = case.task.shape[0]
+        kind = {(0, 0): "loco", (1, 0): "mani", (0, 1): "loco_cc"}[(ep.mode, ep.variant)]; cc = kind == "loco_cc"
+        t = make_task(kind, N); mangle = "_" + type(t).__name__
+        f = lambda a: torch.tensor(np.asarray(a, np.float32))
+        t.fall_penalty = ep.fall_pen; t._max_episode_length = ep.max_episode; t.max_consecutive_successes = ep.max_consec
+        t.max_reset_counts = torch.tensor(ep.max_reset_counts, dtype=torch.long)
+        t.num_successes = torch.tensor(ts.FIXTURE_STATS0[0], dtype=torch.long); t.num_resets = torch.tensor(ts.FIXTURE_STATS0[1], dtype=torch.long)
+        t.baseline_knee_height, t.baseline_height, t.baseline_corner_height = ep.h_knee, ep.h_base, ep.h_corner
+        t.min_joint_23_diff, t.max_joint_23_diff = ep.d23_pen; t.reset_min_joint_23_diff, t.reset_max_joint_23_diff = ep.d23_rst
+        t.min_joint_1_pos, t.max_joint_1_pos = ep.d1_pen[0]; t.reset_min_joint_1_pos, t.reset_max_joint_1_pos = ep.d1_rst[0]
+        corner = f(ep.corner).repeat(N, 1, 1)
+        setattr(t, mangle + "__corner_pos_robot", corner)
+        if kind == "mani":
+            setattr(t, mangle + "__corner_pos_world", transform_vectors(t.default_robot_quaternions_mani, t.default_robot_positions_mani, corner, "cpu"))
+        if cc:
+            t.rot_dist_decreasing_reward_scale = ep.rot_dec_scale; t.no_rot_dist_decreasing_reward_thresh = ep.rot_dec_thresh
+        task = case.task
+        t.last_actions = f(task[:, 0:12]); t.last_base_tip_positions = f(task[:, 24:36]).view(N, 4, 3); t.goal_quaternions = f(task[:, 36:40])
+        if cc:
+            t.current_joint_position_targets_se = f(task[:, 40:52]); t.last_joint_position_targets = f(task[:, 52:64]); t.last_rot_dist = f(task[:, 64])
+        for col, key in enumerate(("successes", "consecutive_successes", "goal_reset_buf", "reset_buf", "progress_buf")):
+            setattr(t, key, torch.tensor(case.cnt[:, col], dtype=torch.long))
+        robot = t.robot_locomotion if kind != "mani" else t.robot_manipulation
+        T = case.steps
+        out[f"{name}/readback"] = np.asarray(case.readback, np.float32).reshape(T, N, 99); out[f"{name}/actions"] = np.asarray(case.actions, np.float32).reshape(T, N, 12)
+        out[f"{name}/task"] = case.task.astype(np.float32); out[f"{name}/cnt"] = case.cnt.astype(np.int64)
+        for step in range(T):
+            rb, act = (f(x) for x in case.step(step))
+            held = t.reset_buf.clone(); t.reset_buf = torch.zeros_like(held)
+            t.pre_physics_step(act.clamp(-1.0, 1.0))          # the clipActions clamp of the wrapper (vec_env_rlgames.py:60)
+            t.reset_buf = held
+            robot.joint_positions, robot.joint_velocities, robot.joint_accelerations = rb[:, 0:12].clone(), rb[:, 12:24].clone(), rb[:, 24:36].clone()
+            robot.tip_positions, robot.knee_positions = rb[:, 49:61].reshape(N, 4, 3).clone(), rb[:, 61:85].reshape(N, 8, 3).clone()
+            pos, quat, lin, ang = rb[:, 36:39].clone(), rb[:, 39:43].clone(), rb[:, 43:46].clone(), rb[:, 46:49].clone()
+            if kind != "mani":
+                robot.base_positions, robot.base_quaternions, robot.base_linear_velocities, robot.base_angular_velocities = pos, quat, lin, ang
+            else:
+                t.obj.pos, t.obj.quat, t.obj.lin, t.obj.ang = pos, quat, lin, ang
+            if cc:
+                t.torque = rb[:, 87:99].clone()
+            t.progress_buf[:] += 1
+            t.get_observations(); t.calculate_metrics(); t.is_done()
+            k = f"{name}/{step}/"
+            keys = sorted(t.extras.keys()); out[f"{name}/extras_keys"] = np.array(keys)
+            out[k + "extras"] = torch.stack([torch.as_tensor(t.extras[x], dtype=torch.float32) for x in keys]).numpy()
+            out[k + "obs"] = t.obs_buf.clone().numpy(); out[k + "states"] = t.states_buf.clone().numpy(); out[k + "rew"] = t.rew_buf.clone().numpy()
+            for key in ("successes", "consecutive_successes", "goal_reset_buf", "reset_buf", "progress_buf"):
+                out[k + key] = getattr(t, key).clone().numpy()
+            out[k + "last_actions"] = t.last_actions.clone().numpy(); out[k + "last_base_tip"] = t.last_base_tip_positions.reshape(N, 12).clone().numpy()
+            if cc:
+                out[k + "last_targets"] = t.last_joint_position_targets.clone().numpy(); out[k + "last_rot_dist"] = t.last_rot_dist.clone().numpy()
+                out[k + "se"] = t.current_joint_position_targets_se.clone().numpy()
+            out[k + "num_successes"] = np.int64(t.num_successes); out[k + "num_resets"] = np.int64(t.num_resets)
+            out[k + "success_rate"] = np.float32(t.success_rate)
+    return out
+
+
 def main():
     assert os.path.isdir(REF_RL), "reference tree not present: golden vectors can only be regenerated in the build container"
+    only_branches = sys.argv[1:] == ["branches"]          # `gen_golden.py branches`: tests/golden/task_branches.npz alone
+    ts, cases = build_branch_cases()
     _install_placeholders()
     sys.path[:0] = [REF_RL, os.path.dirname(REF_RL)]
     os.makedirs(OUT, exist_ok=True)
+    d = gen_branches(ts, cases)
+    np.savez_compressed(os.path.join(OUT, "task_branches.npz"), **d)
+    print("branches", len(cases), "scenarios,", os.path.getsize(os.path.join(OUT, "task_branches.npz")), "bytes")
+    if only_branches:
+        return
     for kind in ("loco", "mani", "loco_cc", "mani_cc", "loco_pc", "mani_pc", "loco_v", "mani_v"):
         d = gen_task(kind, T=26 if kind in ("loco", "mani", "loco_v", "mani_v") else 32)
         np.savez_compressed(os.path.join(OUT, f"task_{kind}.npz"), **d)
