@@ -178,6 +178,66 @@ int lm_rollout_set_trajectory_record(lm_rollout* r, const int32_t* env_ids_host,
 int lm_trajectory_update(struct lm_engine* h, const int32_t* env_ids_dev, int K, const float* rewards, const int64_t* dones, float* rows,
                          int32_t* header, int max_rows, int episode_cap, void* stream);
 
+/* ---- replay of recorded joint motions (csrc/lm_replay.hip): N envs are driven along R recorded joint trajectories (the format of the
+ * reference's RECORD_JOINT files and of the trajectory record's q columns) and every env is scored against its recording where the data lives.
+ * With per-env parameters held (lm_set_env_params) one run scores a whole grid of physics parameters: a parameter fit, or system
+ * identification from joint logs.  No step kernel, launch path or record layout changes: the caller steps with lm_step and calls
+ * lm_replay_update after every step, as lm_episode_update / lm_trajectory_update are used.
+ *
+ * A replay plan belongs to an engine and owns device copies of
+ *   rec float [R][T_max][12]   the joint rows to score against, in the order of robot.joint_positions (state rows R_Q + 0..11)
+ *   act float [R][T_max][12]   the open-loop action applied at step s (row 0: the reset step, conventionally zero)
+ *   len int32 [R]              rows of each recording, window_rows <= len <= T_max
+ *   env_rec int32 [N]          which recording env e replays; -1: the env takes no part (zero actions, its record column is never written)
+ * lm_replay_create is SYNCHRONOUS (blocking copies, like lm_rollout_set_trajectory_record).  servo != 0 replaces the action table by a
+ * proportional steer back onto the recording (below); hold in [0, 8] further zero-action rows are scored after a recording's last row
+ * (returns and termination only) so that a success streak that started late can complete; inv_full = 1 / (act_scale x control period), the
+ * reciprocal of the joint displacement of a saturated action, computed by the caller (the product build divides to 1 ulp);
+ * v2_thresh = sin^2(thresh / 2) for the success window thresh of the task (rot_dist = 2 asin |v| <= thresh  <=>  |v|^2 <= v2_thresh);
+ * track_tol the joint-step error below which a joint-step counts as tracked.
+ * LM_EINVAL (-1, reason in lm_last_error; nothing is allocated) for: a null argument; R < 1; T_max < 1; a length outside [window_rows, T_max]
+ * (window_rows < 1 included); an id outside [-1, R); hold outside [0, 8]; a table entry, inv_full, v2_thresh or track_tol that is not finite;
+ * a calling thread whose current device is not the engine's; an engine with a block that is not variant 0 in LM_DRIVE_VELOCITY with 64-wide
+ * observations (PD targets are not joint-rate actions).  -2 if an allocation or copy fails.
+ *
+ * lm_replay_update is called after lm_step number s (s = 0 is the reset step: call it on an engine whose envs are all about to reset), on the
+ * stream the step was enqueued on: ONE launch, one thread per env, SoA accesses, no atomics.  It reads LM_PTR_STATE rows R_Q + 0..11,
+ * LM_PTR_CNT rows 2 (goal_reset_buf) and 3 (reset_buf), obs [N][64] and rewards [N] as that step wrote them (obs columns 7..9, the vector
+ * part of the orientation error, are far below any clip), and writes
+ *   record float [LM_REPLAY_ROWS][N]   caller-owned; before step 0: rows 2 and 9 = -1, row 11 = +inf, everything else 0
+ *   actions_next float [N][12]         the actions of step s + 1 (may be the buffer step s read)
+ * Rule per env with r = env_rec[e] >= 0 and T = len[r]; fp32, in the order written, no contraction:
+ *   if (finished || s >= T + hold) { actions_next = 0; return; }
+ *   q_j = state[R_Q + j][e];  v2 = (o7*o7 + o8*o8) + o9*o9  (obs[e][7..9]);  rew = rewards[e]
+ *   if (s < T) {
+ *     d_j = q_j - rec[r][s][j];  m = max_j |d_j|
+ *     if (s == 0) { row0_err = m; v2_first = v2; }
+ *     qerr = max(qerr, m);  abs_sum += sum_j |d_j|;  sq_sum += sum_j d_j^2
+ *     if (s >= 1) { e_j = (q_j - qprev_j) - (rec[r][s][j] - rec[r][s-1][j]);  tracked += #{ |e_j| < track_tol };  if (s <= 4) early += sum_j |e_j|; }
+ *     if (v2 <= v2_thresh) { if (first_succ < 0) first_succ = s;  if (s >= T - window_rows) in_window += 1; }
+ *     min_v2 = min(min_v2, v2);  if (s >= T - window_rows) window_return += rew;
+ *     rows += 1;  qprev = q;
+ *   }
+ *   ret += rew;
+ *   if (cnt[3][e] != 0) { finished = 1; done_at = s; goal_at_done = (cnt[2][e] != 0); }
+ *   actions_next_j = (finished || s + 1 >= T) ? 0 : servo ? clamp((rec[r][s+1][j] - q_j) * inv_full, -1, 1) : act[r][s+1][j]
+ * (the sums over j run j = 0 .. 11 from zero and are then added to the running value).  An env with r = -1 gets actions_next = 0.
+ * Record rows:  0 rows | 1 finished | 2 done_at | 3 goal_at_done | 4 row0_err | 5 qerr | 6 sq_sum | 7 tracked | 8 early | 9 first_succ |
+ *   10 in_window | 11 min_v2 | 12 ret | 13 window_return | 14 v2_first | 15 abs_sum | 16-27 qprev | 28-31 never written.
+ * Counts and rows are floats: exact below 2^24.  The rule restates the host replay the project's evidence was produced with: rows up to and
+ * including the terminal row, statistics over recorded rows only, `hold` zero-action rows after the recording; one difference: a reset flag
+ * raised on row 0 ends the replay.
+ * lm_replay_update returns LM_EINVAL for a null argument, s < 0, actions_next that is not 16-byte aligned (an env's 12 actions leave as three
+ * 16-byte stores) or a foreign device - nothing is launched; -2 for a launch failure.  lm_replay_steps: the number of
+ * steps a run takes, max over the recordings in use of len + hold (0 when no env takes part; LM_EINVAL for a null plan). */
+#define LM_REPLAY_ROWS 32
+typedef struct lm_replay lm_replay;
+int lm_replay_create(lm_replay** out, struct lm_engine* h, const float* rec_host, const float* act_host, const int32_t* len_host, int R, int T_max,
+                     const int32_t* env_rec_host, int servo, int hold, int window_rows, float inv_full, float v2_thresh, float track_tol);
+int lm_replay_steps(const lm_replay* p);
+int lm_replay_update(lm_replay* p, int s, const float* obs, const float* rewards, float* record, float* actions_next, void* stream);
+int lm_replay_destroy(lm_replay* p);
+
 /* ---- PPO update (csrc/lm_ppo.hip): the loss and parameter gradient of one mini-batch of train/ppo.py PPO.update for the MLP policy above,
  * and GAE.  The optimiser, the gradient-norm clip, the KL-adaptive rate and the scalers stay with the caller.
  *

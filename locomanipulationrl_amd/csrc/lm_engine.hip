@@ -1165,6 +1165,12 @@ void lm_internal_trajectory_info(const lm_engine* h, int* split, int* free_body_
   *split = h->split;
   for (int b = 0; b < 2; b++) free_body_row[b] = h->h_params[h->n_tasks == 2 ? b : 0].mode == LM_MODE_LOCO ? R_FB0 : R_FB1;
 }
+void lm_internal_replay_info(const lm_engine* h, int* variant, int* drive_mode, int* num_obs) {
+  for (int b = 0; b < 2; b++) {
+    const lm_params& p = h->h_params[h->n_tasks == 2 ? b : 0];
+    variant[b] = p.variant; drive_mode[b] = p.drive_mode; num_obs[b] = p.num_obs;
+  }
+}
 
 uint64_t lm_internal_args_key(const lm_engine* h) {
   return h ? ((uint64_t)h->seed | ((uint64_t)((h->view_obs ? 1 : 0) | (h->view_states ? 2 : 0) | (h->view_terms ? 4 : 0) | (h->contact_on ? 8 : 0) | (h->d_env_params ? 16 : 0)) << 32)) : 0ull;

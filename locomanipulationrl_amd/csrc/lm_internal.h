@@ -33,6 +33,9 @@ void lm_internal_episode_info(const lm_engine* h, int* split, int* max_episode);
 // what the trajectory record needs of the engine: the same split, and per parameter block the state row its free body starts at (R_FB0, the
 // base, for a locomotion block; R_FB1, the plate, for a manipulation block)
 void lm_internal_trajectory_info(const lm_engine* h, int* split, int* free_body_row);
+// what a replay plan (lm_replay.hip) checks of the engine: per parameter block (both entries the same with one block) the task variant, the
+// drive mode and the observation width
+void lm_internal_replay_info(const lm_engine* h, int* variant, int* drive_mode, int* num_obs);
 // what a captured lm_step launch has baked into its kernel arguments and the engine may change afterwards: the goal / domain-randomisation seed
 // (lm_set_seed), which of the unclipped views are kept current (lm_ptr), and which kernels lm_step launches (lm_enable_contact_forces,
 // lm_enable_env_params).  A hipGraph captured under another key is re-captured.

@@ -26,6 +26,10 @@ EPISODE_ROWS = 9         # LM_EPISODE_ROWS (include/lm_policy.h)
 # rows of the episode record
 EPISODE = dict(running_return=0, running_length=1, episodes=2, sum_return=3, sum_length=4, goal=5, timeout=6, failure=7, last_return=8)
 TRAJ_COLS, TRAJ_MAX_ENVS = 64, 256      # LM_TRAJ_COLS, LM_TRAJ_MAX_ENVS (include/lm_policy.h)
+REPLAY_ROWS = 32         # LM_REPLAY_ROWS (include/lm_policy.h)
+# rows of the replay record (qprev: the first of 12)
+REPLAY = dict(rows=0, finished=1, done_at=2, goal=3, row0_err=4, qerr=5, sq_sum=6, tracked=7, early=8, first_succ=9, in_window=10, min_v2=11, ret=12,
+              window_return=13, v2_first=14, abs_sum=15, qprev=16)
 PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS, PTR_CONTACT, PTR_DR_ACTUATOR = range(14)
 PTR_ENV_PARAMS = 14      # LM_PTR_ENV_PARAMS
 ENV_PARAM_ROWS = DR_PHYS_ROWS + DR_MASS_ROWS + DR_ACTUATOR_ROWS      # LM_ENV_PARAM_ROWS = 69: the three records one after the other
@@ -70,6 +74,7 @@ EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy",
            "lm_rollout_set_deterministic", "lm_rollout_set_episode_record", "lm_episode_update",
            "lm_rollout_set_trajectory_record", "lm_trajectory_update",
+           "lm_replay_create", "lm_replay_steps", "lm_replay_update", "lm_replay_destroy",
            "lm_mlp_grad_param_count", "lm_mlp_ppo_grad", "lm_mlp_ppo_grad_workspace", "lm_mlp_ppo_grad_geometry", "lm_gae",
            "lm_gnn_grad_param_count", "lm_gnn_ppo_grad", "lm_gnn_ppo_grad_workspace", "lm_gnn_ppo_grad_geometry",
            "lm_optim_state_len", "lm_optim_state_init", "lm_adam_clip_step", "lm_kl_adaptive_lr",
@@ -246,7 +251,7 @@ def hipcc_command(extra, out):
     # LDS stores) needs no v_accvgpr_read per element (504 of them in k_gnn_forward)
     return [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
             "-mllvm", "-amdgpu-mfma-vgpr-form", "-fPIC", "-shared", *extra, os.path.join(_CSRC, "lm_engine.hip"), os.path.join(_CSRC, "lm_engine_w2.hip"), os.path.join(_CSRC, "lm_engine_h2.hip"), os.path.join(_CSRC, "lm_engine_h3.hip"), os.path.join(_CSRC, "lm_engine_ev.hip"), os.path.join(_CSRC, "lm_engine_tr.hip"), os.path.join(_CSRC, "lm_engine_hp.hip"),
-            os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), os.path.join(_CSRC, "lm_gnn_ppo.hip"), os.path.join(_CSRC, "lm_optim.hip"), os.path.join(_CSRC, "lm_prepare.hip"), "-o", out]
+            os.path.join(_CSRC, "lm_policy.hip"), os.path.join(_CSRC, "lm_ppo.hip"), os.path.join(_CSRC, "lm_gnn_ppo.hip"), os.path.join(_CSRC, "lm_optim.hip"), os.path.join(_CSRC, "lm_prepare.hip"), os.path.join(_CSRC, "lm_replay.hip"), "-o", out]
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
@@ -312,6 +317,10 @@ def load_library() -> C.CDLL:
     lib.lm_episode_update.argtypes = [vp, fp, vp, fp, ip, vp]
     lib.lm_rollout_set_trajectory_record.argtypes = [vp, vp, ip, fp, vp, ip, ip]
     lib.lm_trajectory_update.argtypes = [vp, vp, ip, fp, vp, fp, vp, ip, ip, vp]
+    lib.lm_replay_create.argtypes = [C.POINTER(vp), vp, fp, fp, vp, ip, ip, vp, ip, ip, ip, C.c_float, C.c_float, C.c_float]
+    lib.lm_replay_steps.argtypes = [vp]
+    lib.lm_replay_update.argtypes = [vp, ip, fp, fp, fp, fp, vp]
+    lib.lm_replay_destroy.argtypes = [vp]
     lib.lm_mlp_grad_param_count.argtypes = [ip]
     lib.lm_mlp_ppo_grad.argtypes = [fp, fp, fp, fp, fp, fp, fp, ip, ip, C.POINTER(LmPpoHyper), fp, fp, vp, C.c_longlong, vp]
     lib.lm_mlp_ppo_grad_workspace.argtypes = [ip, ip]; lib.lm_mlp_ppo_grad_workspace.restype = C.c_longlong
@@ -379,6 +388,7 @@ class Engine:
                     with torch.cuda.device(self.device):
                         self._check(getattr(self.lib, setter)(self._h, b, C.byref(dr)))
         self.seed = int(seed) & 0xFFFFFFFF
+        self.params = params                     # the parameter blocks as handed in (host side: what a ReplayPlan reads act_scale and the control period from)
         self.split_env = int(split_env) if (split_env and len(params) == 2) else None      # first env of the second parameter block (co-training)
         N = self.num_envs
         self.state = self._wrap(PTR_STATE, (STATE_ROWS, N), "<f4")
@@ -1002,3 +1012,161 @@ class TrajectoryRecord:
             np.savez(base + ".npz", **arrays)
             paths.append(base + ".npy")
         return paths
+
+
+class ReplayRecord:
+    """The replay record of include/lm_policy.h: a float (32, N) tensor on the engine's device - per env how far the replay of its recording
+    got, how it ended and how close the joints and the orientation error stayed to the recording (rows: REPLAY).  A ReplayPlan fills it
+    (plan.run(record), or record.update(plan, s, ...) after every engine step); zero() starts a measurement.  On an engine without the C
+    library (CPU tensors: the oracle backend of the tests) update() applies the same rule in torch, in fp32 and in the order of the header."""
+
+    def __init__(self, engine):
+        import torch
+        self.torch, self.engine, self.N = torch, engine, int(engine.num_envs)
+        self.record = torch.empty((REPLAY_ROWS, self.N), dtype=torch.float32, device=engine.cnt.device)
+        self._native = hasattr(engine, "lib") and hasattr(engine, "_h")
+        self.full = None          # joint displacement of a saturated action: set by the plan that fills the record (summary()'s `early` is in its units)
+        self.zero()
+
+    def zero(self):
+        self.record.zero_()
+        self.record[REPLAY["done_at"]] = -1.0; self.record[REPLAY["first_succ"]] = -1.0; self.record[REPLAY["min_v2"]] = float("inf")
+
+    def update(self, plan, s: int, obs, rew, actions_next):
+        """After engine step number s (0: the reset step): obs (N, 64) and rew (N,) as that step wrote them; actions_next (N, 12) receives the
+        actions of step s + 1 (it may be the tensor step s read)."""
+        e, torch = self.engine, self.torch
+        assert plan.engine is e, "the plan drives another engine"
+        self.full = plan.full
+        if self._native:
+            e._f32(obs, (self.N, NUM_OBS)); e._f32(rew, (self.N,)); e._f32(actions_next, (self.N, NUM_ACTIONS))
+            with torch.cuda.device(e.device):
+                e._check(e.lib.lm_replay_update(plan._h, int(s), Engine._p(obs), Engine._p(rew), Engine._p(self.record), Engine._p(actions_next), e._stream()))
+            return
+        R = self.record; dev = R.device; s = int(s)
+        f32 = lambda x: x.to(dev, torch.float32)
+        r = plan.env_rec_t.to(dev).long(); part = r >= 0; rr = r.clamp(min=0)
+        T = plan.len_t.to(dev).long()[rr]
+        live = part & (R[1] == 0) & (s < T + plan.hold)
+        q = f32(e.state[ROW["q"]:ROW["q"] + 12]); o = f32(obs); rw = f32(rew)
+        v2 = (o[:, 7] * o[:, 7] + o[:, 8] * o[:, 8]) + o[:, 9] * o[:, 9]
+        rec = plan.rec_t.to(dev); row = lambda k: rec[rr, min(max(k, 0), plan.T_max - 1)].T           # (12, N); only read where row k exists
+        put = lambda i, mask, val: R.__setitem__(i, torch.where(mask, val, R[i]))
+        seqsum = lambda x: sum((x[j] for j in range(1, 12)), x[0])          # j = 0 .. 11, in order
+        inrec = live & (s < T)
+        rs = row(s); d = q - rs; ad = d.abs(); m = ad.max(0).values
+        if s == 0:
+            put(4, inrec, m); put(14, inrec, v2)
+        put(5, inrec, torch.maximum(R[5], m)); put(15, inrec, R[15] + seqsum(ad)); put(6, inrec, R[6] + seqsum(d * d))
+        if s >= 1:
+            ej = ((q - R[16:28]) - (rs - row(s - 1))).abs()
+            put(7, inrec, R[7] + (ej < plan.track_tol).sum(0).to(torch.float32))
+            if s <= 4:
+                put(8, inrec, R[8] + seqsum(ej))
+        win = s >= T - plan.window_rows; ok = inrec & (v2 <= plan.v2_thresh)
+        put(9, ok & (R[9] < 0), torch.full_like(v2, float(s))); put(10, ok & win, R[10] + 1.0)
+        put(11, inrec, torch.minimum(R[11], v2)); put(13, inrec & win, R[13] + rw); put(0, inrec, R[0] + 1.0)
+        R[16:28] = torch.where(inrec[None], q, R[16:28])
+        put(12, live, R[12] + rw)
+        cnt = e.cnt.to(dev); fin = live & (cnt[3] != 0)
+        put(1, fin, torch.ones_like(v2)); put(2, fin, torch.full_like(v2, float(s))); put(3, fin, (cnt[2] != 0).to(torch.float32))
+        go = live & ~fin & (s + 1 < T)
+        nxt = ((row(s + 1) - q) * plan.inv_full).clamp(-1.0, 1.0) if plan.servo else plan.act_t.to(dev)[rr, min(s + 1, plan.T_max - 1)].T
+        actions_next.copy_(torch.where(go[None], nxt, torch.zeros_like(nxt)).T.to(actions_next.device))
+
+    def summary(self):
+        """Host reduction per env, the quantities of the project's host replay (numpy arrays of shape (N,); envs that took no part have rows 0):
+        rows, done_at and first_succ (-1: never), goal, row0_err, qerr, rms and mean_abs (joint error over the recorded rows), tracked (share
+        of joint-steps within track_tol), early (mean joint-step error of the first four steps in units of a saturated action; needs the
+        plan's `full`), in_window, min_rd and rd_first = 2 asin(sqrt(v2)), return and window_return."""
+        rec = self.record.detach().cpu().double().numpy()
+        rows = rec[0]; steps = np.maximum(rows - 1.0, 0.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rd = lambda v2: 2.0 * np.arcsin(np.sqrt(np.clip(v2, 0.0, 1.0)))
+            return dict(rows=rows.astype(np.int64), finished=rec[1] != 0, done_at=rec[2].astype(np.int64), goal=rec[3].astype(np.int64), row0_err=rec[4], qerr=rec[5],
+                        rms=np.sqrt(rec[6] / (12.0 * rows)), mean_abs=rec[15] / (12.0 * rows), tracked=rec[7] / (12.0 * steps),
+                        early=rec[8] / (12.0 * np.minimum(4.0, steps) * (self.full if self.full else np.nan)), first_succ=rec[9].astype(np.int64),
+                        in_window=rec[10].astype(np.int64), min_rd=rd(rec[11]), rd_first=rd(rec[14]), window_return=rec[13], **{"return": rec[12]})
+
+
+class ReplayPlan:
+    """A replay plan of include/lm_policy.h: N envs of `engine` driven along recorded joint trajectories and scored against them on the device.
+    `recordings` is a list of (L, 12) arrays (joint order of robot.joint_positions: the reference's RECORD_JOINT files, TrajectoryRecord.save_npy);
+    `env_rec` (N,) names the recording each env replays, -1 for an env that takes no part.  `actions` (a list of (L, 12) arrays: the action
+    applied at every row, row 0 the reset step's) defaults to the actions recovered from the recording, [0, clip(diff(rec) / full, +-1)] with
+    full = act_scale x control period of the engine's blocks, computed in float64 and cast to float32.  servo=True steers every joint back onto
+    the recording each step instead; `hold` zero-action rows follow a recording so that a late success streak can complete; `window_rows` and
+    `succ_thresh` are the task's success window (rows and rot_dist in radians), `track_tol` the joint-step error that counts as tracked.
+    Velocity-drive engines with 64-wide observations only (the library refuses the others).  On an engine without the C library (the oracle
+    backend of the tests) the plan keeps its tables as torch tensors and ReplayRecord.update applies the rule in torch."""
+
+    def __init__(self, engine, recordings, env_rec, actions=None, servo: bool = False, hold: int = 2, window_rows: int = 17, succ_thresh: float = 0.15,
+                 track_tol: float = 1e-3):
+        import torch
+        self.torch, self.engine, self.N = torch, engine, int(engine.num_envs)
+        recs = [np.asarray(a, dtype=np.float64) for a in recordings]
+        if not recs or any(a.ndim != 2 or a.shape[1] != NUM_ACTIONS or a.shape[0] < 1 for a in recs):
+            raise ValueError("recordings: a non-empty list of (L, 12) arrays is needed")
+        fulls = {float(p.act_scale) * float(p.ctrl_dt) for p in engine.params}
+        if len(fulls) != 1:
+            raise ValueError(f"the engine's blocks differ in act_scale x control period ({sorted(fulls)}): one plan scales every action alike")
+        self.full = fulls.pop()
+        if actions is None:
+            acts = [np.concatenate([np.zeros((1, NUM_ACTIONS)), np.clip(np.diff(a, axis=0) / self.full, -1.0, 1.0)]) for a in recs]
+        else:
+            acts = [np.asarray(a, dtype=np.float64) for a in actions]
+            if len(acts) != len(recs) or any(a.shape != b.shape for a, b in zip(acts, recs)):
+                raise ValueError("actions: one (L, 12) array per recording is needed, of the recording's shape")
+        ids = np.asarray(env_rec.detach().cpu().numpy() if hasattr(env_rec, "detach") else env_rec)
+        if ids.shape != (self.N,) or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError(f"env_rec: an integer array of shape ({self.N},) is needed, got {ids.dtype} {ids.shape}")
+        self.R, self.T_max = len(recs), max(a.shape[0] for a in recs)
+        rec = np.zeros((self.R, self.T_max, NUM_ACTIONS), dtype=np.float32); act = np.zeros_like(rec)
+        for k, (a, b) in enumerate(zip(recs, acts)):
+            rec[k, :a.shape[0]] = a; act[k, :a.shape[0]] = b
+        lens = np.asarray([a.shape[0] for a in recs], dtype=np.int32); ids = np.ascontiguousarray(ids, dtype=np.int32)
+        self.servo, self.hold, self.window_rows = bool(servo), int(hold), int(window_rows)
+        self.inv_full = float(np.float32(1.0 / self.full)); self.v2_thresh = float(np.float32(np.sin(0.5 * float(succ_thresh)) ** 2)); self.track_tol = float(np.float32(track_tol))
+        dev = engine.cnt.device
+        self.rec_t, self.act_t = torch.from_numpy(rec).to(dev), torch.from_numpy(act).to(dev)
+        self.len_t, self.env_rec_t = torch.from_numpy(lens).to(dev), torch.from_numpy(ids).to(dev)
+        self._native = hasattr(engine, "lib") and hasattr(engine, "_h")
+        self._h = C.c_void_p()
+        if self._native:
+            p = lambda a: a.ctypes.data_as(C.c_void_p)
+            with torch.cuda.device(engine.device):
+                engine._check(engine.lib.lm_replay_create(C.byref(self._h), engine._h, p(rec), p(act), p(lens), self.R, self.T_max, p(ids), int(self.servo), self.hold,
+                                                          self.window_rows, self.inv_full, self.v2_thresh, self.track_tol))
+            self.steps = int(engine.lib.lm_replay_steps(self._h))
+        else:          # the library's refusals, for a backend without it
+            if any(int(p.variant) != 0 or int(p.drive_mode) != 0 or int(p.num_obs) != NUM_OBS for p in engine.params):
+                raise ValueError("every block must be variant 0 in velocity drive with 64-wide observations (PD targets are not joint-rate actions)")
+            if not np.isfinite(rec).all() or not np.isfinite(act).all():
+                raise ValueError("a table entry is not finite")
+            if not 0 <= self.hold <= 8 or self.window_rows < 1 or (lens < self.window_rows).any() or ids.min() < -1 or ids.max() >= self.R:
+                raise ValueError("hold must be in [0, 8], every recording at least window_rows long and every id in [-1, R)")
+            self.steps = int(max((int(lens[r]) + self.hold for r in set(ids[ids >= 0].tolist())), default=0))
+
+    def run(self, record: ReplayRecord, zero: bool = True):
+        """Replay on an engine whose envs are all about to reset (a fresh engine, or after reset_all()): for s = 0 .. steps - 1, Engine.step(actions)
+        and then the record update, which also writes the next actions; nothing waits for the host inside the loop.  Returns the record."""
+        e, torch = self.engine, self.torch
+        dev = e.cnt.device
+        if zero:
+            record.zero()
+        actions = torch.zeros((self.N, NUM_ACTIONS), dtype=torch.float32, device=dev)
+        obs = torch.empty((self.N, NUM_OBS), dtype=torch.float32, device=dev); rew = torch.empty((self.N,), dtype=torch.float32, device=dev)
+        for s in range(self.steps):
+            e.step(actions, out_obs=obs, out_rew=rew)
+            record.update(self, s, obs, rew, actions)
+        return record
+
+    def close(self):
+        if self._h:
+            self.engine.lib.lm_replay_destroy(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
