@@ -331,10 +331,15 @@ int lm_enable_env_params(lm_engine* h);
  * that is not finite; a mass, the plate's inertia factor, kp or kd that is not > 0; mu, a max effort, a max joint velocity or a joint damping
  * that is < 0; a latency that is not whole or outside [0, substeps] of a block that reads it; a row that no block of the engine reads: kp
  * without a position gain (variant 0 in velocity or effort drive), kd in effort drive, latency on variant 0, the plate rows on an engine
- * without a manipulation block.  The copy is blocking. */
+ * without a manipulation block.
+ * SYNCHRONOUS against the whole device: after the validation the call waits for the device (hipDeviceSynchronize) before it touches the table or
+ * the mask, and its copies are blocking.  When it returns, every lm_step enqueued before it - on any stream, the caller's non-blocking ones
+ * included - has run with the rows as they were, and every later one sees the new rows.  Not to be called while a graph that contains lm_step
+ * is being captured (like lm_enable_env_params); a graph captured before it needs no re-capture. */
 int lm_set_env_params(lm_engine* h, int row0, int nrows, const float* values_host);
 /* Rows [row0, row0 + nrows) follow their channel - or the nominal value - again from the next step on.  A mass / actuator record row that no
- * channel writes shows the nominal value again.  Blocking. */
+ * channel writes shows the nominal value again.  Synchronous against the whole device in the same way as lm_set_env_params: it waits for the
+ * device before it changes the mask or rewrites a record row, so steps enqueued before it still run with the rows held. */
 int lm_clear_env_params(lm_engine* h, int row0, int nrows);
 /* mask_out[0] bit r: row r (< 64) is held; mask_out[1] bit r - 64: row r.  LM_EINVAL: null argument, or not enabled. */
 int lm_env_params_held(const lm_engine* h, uint64_t* mask_out);

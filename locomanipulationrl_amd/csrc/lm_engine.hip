@@ -994,6 +994,9 @@ int lm_set_env_params(lm_engine* h, int row0, int nrows, const float* values_hos
     for (size_t e = 0; e < N; e++)
       if (const char* why = env_value_refusal(h, r, e, row[e])) return fail_fn(LM_EINVAL, fn, why);
   }
+  // every step enqueued before this call, on whichever stream, runs with the rows as they were: a blocking copy alone is ordered against the
+  // null stream only, and would overtake work queued on a caller's non-blocking stream
+  HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(h->d_env_params + (size_t)row0 * N, values_host, (size_t)nrows * N * sizeof(float), hipMemcpyHostToDevice));
   for (int r = row0; r < row0 + nrows; r++) h->env_mask[r >> 6] |= 1ull << (r & 63);
   return env_mask_upload(h);
@@ -1003,6 +1006,7 @@ int lm_clear_env_params(lm_engine* h, int row0, int nrows) {
   const char* const fn = "lm_clear_env_params";
   if (int rc = env_params_entry(fn, h, row0, nrows)) return rc;
   const size_t N = (size_t)h->N;
+  HIPCHK(hipDeviceSynchronize());      // as in lm_set_env_params: the mask and the record rows below are read by steps that may still be queued
   for (int r = row0; r < row0 + nrows; r++) {
     if (!((h->env_mask[r >> 6] >> (r & 63)) & 1ull)) continue;
     h->env_mask[r >> 6] &= ~(1ull << (r & 63));

@@ -502,6 +502,7 @@ class Engine:
     def set_env_params(self, **named):
         """Hold the named groups (ENV_PARAMS) at per-env values: SoA arrays / tensors of env_param_shape(name, N), or a scalar for every env.
         Every later step uses them in place of what the group's channel draws (or of the nominal value); the dr_* records report them.
+        The call waits for the device first: a step enqueued before it, on any stream, still runs with the rows as they were.
         Validated by the library (EngineError, nothing changed) - finite; masses, plate_inertia_factor, kp, kd > 0; mu, max_efforts,
         max_velocities, joint_damping >= 0; latency whole in [0, substeps]; groups the engine's blocks do not read are refused.  Names and
         shapes of all groups are checked first (ValueError); each group is then one library call, so the groups in front of a refused one
@@ -513,7 +514,8 @@ class Engine:
                 self._check(self.lib.lm_set_env_params(self._h, row0, a.shape[0], a.ctypes.data_as(C.c_void_p)))
 
     def clear_env_params(self, *names):
-        """The named groups follow their channel (or the nominal value) again; without names, all of them."""
+        """The named groups follow their channel (or the nominal value) again from the next step on; without names, all of them.  Waits for
+        the device first, as set_env_params does: steps enqueued before the call still run with the rows held."""
         spans = [env_param_rows(k) for k in names] or [(0, ENV_PARAM_ROWS)]
         self._env_table()
         with self.torch.cuda.device(self.device):
