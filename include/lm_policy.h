@@ -223,17 +223,50 @@ int lm_trajectory_update(struct lm_engine* h, const int32_t* env_ids_dev, int K,
  *   actions_next_j = (finished || s + 1 >= T) ? 0 : servo ? clamp((rec[r][s+1][j] - q_j) * inv_full, -1, 1) : act[r][s+1][j]
  * (the sums over j run j = 0 .. 11 from zero and are then added to the running value).  An env with r = -1 gets actions_next = 0.
  * Record rows:  0 rows | 1 finished | 2 done_at | 3 goal_at_done | 4 row0_err | 5 qerr | 6 sq_sum | 7 tracked | 8 early | 9 first_succ |
- *   10 in_window | 11 min_v2 | 12 ret | 13 window_return | 14 v2_first | 15 abs_sum | 16-27 qprev | 28-31 never written.
+ *   10 in_window | 11 min_v2 | 12 ret | 13 window_return | 14 v2_first | 15 abs_sum | 16-27 qprev | 28 saturated | 29 cmd_err (both: PD plans in
+ *   targets mode only, below; otherwise never written) | 30-31 never written.
  * Counts and rows are floats: exact below 2^24.  The rule restates the host replay the project's evidence was produced with: rows up to and
  * including the terminal row, statistics over recorded rows only, `hold` zero-action rows after the recording; one difference: a reset flag
  * raised on row 0 ends the replay.
  * lm_replay_update returns LM_EINVAL for a null argument, s < 0, actions_next that is not 16-byte aligned (an env's 12 actions leave as three
  * 16-byte stores) or a foreign device - nothing is launched; -2 for a launch failure.  lm_replay_steps: the number of
- * steps a run takes, max over the recordings in use of len + hold (0 when no env takes part; LM_EINVAL for a null plan). */
+ * steps a run takes, max over the recordings in use of len + hold (0 when no env takes part; LM_EINVAL for a null plan).
+ *
+ * PD-actuator engines: lm_replay_create_pd makes a plan of the same type for an engine whose every block is variant 1 (custom controller,
+ * 88-wide observations), variant 2 (position control) or variant 0 in LM_DRIVE_POSITION; co-training engines with two such blocks are
+ * accepted and an env's block is chosen by the engine's split_env.  What such a robot logs is a command log plus measured joints:
+ *   rec float [R][T_max][12]   the joint rows to score against, as above
+ *   cmd float [R][T_max][12]   LM_REPLAY_CMD_ACTIONS: cmd[r][s] = the action applied at step s (row 0: the reset step's; the trajectory
+ *                              record's last_actions columns are these);  LM_REPLAY_CMD_TARGETS: cmd[r][s] = the 12 joint position targets
+ *                              commanded for step s, in the joint order of rec
+ * len, env_rec, hold, window_rows, v2_thresh and track_tol as above.  The plan reads variant, act_scale_se, act_scale and num_obs from the
+ * engine's own blocks; the caller passes no scale.  The reciprocals inv_act_scale_se = 1 / act_scale_se (variants 1 / 2) and
+ * inv_act_scale = 1 / act_scale (variant 0) are formed once on the host, in float.  LM_EINVAL (reason in lm_last_error; nothing is
+ * allocated) for everything lm_replay_create refuses except the engine family, and for a block in velocity or effort drive, a cmd_mode
+ * outside {0, 1} and a cmd entry that is not finite.  lm_replay_steps and lm_replay_destroy serve both kinds of plan.
+ * lm_replay_update on a PD plan takes obs [N][lm_num_obs(engine)] (columns 7..9 are the orientation-error vector in all three layouts) and
+ * launches k_replay_update_pd: one thread per env, SoA accesses, no atomics, no LDS, no contraction.  The scoring rule above stays word for
+ * word (rows 0..27, finished, hold, the window).  The last line of the rule becomes, with se_j = state[R_SE + j][e] as step s left it:
+ *   actions mode:  actions_next_j = (finished || s + 1 >= T) ? 0 : cmd[r][s+1][j]
+ *   targets mode, for a not-finished env with s + 1 < T (otherwise actions_next = 0), t = cmd[r][s+1]:
+ *     variants 1 / 2:  for limb l = 0 .. 3 (rows l: dof1, 4+2l: swing, 5+2l: extension - the indices the step uses for R_Q and R_SE)
+ *                        c[l] = t[l];  c[4+2l] = 0.5f * (t[4+2l] + t[5+2l]);  c[5+2l] = t[4+2l] - t[5+2l];      (the inverse of the step's targets)
+ *                      raw_j = (c_j - se_j) * inv_act_scale_se
+ *     variant 0 in LM_DRIVE_POSITION:  raw_j = t_j * inv_act_scale
+ *     actions_next_j = clamp(raw_j, -1, 1);  saturated += #{ j : |raw_j| > 1 }
+ *   targets mode, variants 1 / 2, 1 <= s < T (inside the `if (s < T)` block), c formed from t = cmd[r][s] as above:
+ *     cmd_err = max(cmd_err, max_j |c_j - se_j|)      the command the engine holds after step s against the command logged for it
+ * A saturated count or a cmd_err above rounding says that the log cannot be reproduced through this task's rate-limited (act_scale_se per
+ * step), range-limited (se_lo .. se_hi) action interface.  In actions mode and on velocity plans rows 28 and 29 are never written. */
 #define LM_REPLAY_ROWS 32
+#define LM_REPLAY_CMD_ACTIONS 0   /* cmd[r][s] = the action applied at step s (row 0: the reset step's) */
+#define LM_REPLAY_CMD_TARGETS 1   /* cmd[r][s] = the 12 joint position targets commanded for step s, joint order of rec */
 typedef struct lm_replay lm_replay;
 int lm_replay_create(lm_replay** out, struct lm_engine* h, const float* rec_host, const float* act_host, const int32_t* len_host, int R, int T_max,
                      const int32_t* env_rec_host, int servo, int hold, int window_rows, float inv_full, float v2_thresh, float track_tol);
+int lm_replay_create_pd(lm_replay** out, struct lm_engine* h, const float* rec_host, const float* cmd_host, const int32_t* len_host,
+                        int R, int T_max, const int32_t* env_rec_host, int cmd_mode, int hold, int window_rows,
+                        float v2_thresh, float track_tol);
 int lm_replay_steps(const lm_replay* p);
 int lm_replay_update(lm_replay* p, int s, const float* obs, const float* rewards, float* record, float* actions_next, void* stream);
 int lm_replay_destroy(lm_replay* p);

@@ -1169,11 +1169,14 @@ void lm_internal_trajectory_info(const lm_engine* h, int* split, int* free_body_
   *split = h->split;
   for (int b = 0; b < 2; b++) free_body_row[b] = h->h_params[h->n_tasks == 2 ? b : 0].mode == LM_MODE_LOCO ? R_FB0 : R_FB1;
 }
-void lm_internal_replay_info(const lm_engine* h, int* variant, int* drive_mode, int* num_obs) {
+void lm_internal_replay_info(const lm_engine* h, int* variant, int* drive_mode, int* num_obs, int* split, float* act_scale, float* act_scale_se) {
   for (int b = 0; b < 2; b++) {
     const lm_params& p = h->h_params[h->n_tasks == 2 ? b : 0];
     variant[b] = p.variant; drive_mode[b] = p.drive_mode; num_obs[b] = p.num_obs;
+    if (act_scale) act_scale[b] = p.act_scale;
+    if (act_scale_se) act_scale_se[b] = p.act_scale_se;
   }
+  if (split) *split = h->split;
 }
 
 uint64_t lm_internal_args_key(const lm_engine* h) {

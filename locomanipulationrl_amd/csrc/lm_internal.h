@@ -34,8 +34,9 @@ void lm_internal_episode_info(const lm_engine* h, int* split, int* max_episode);
 // base, for a locomotion block; R_FB1, the plate, for a manipulation block)
 void lm_internal_trajectory_info(const lm_engine* h, int* split, int* free_body_row);
 // what a replay plan (lm_replay.hip) checks of the engine: per parameter block (both entries the same with one block) the task variant, the
-// drive mode and the observation width
-void lm_internal_replay_info(const lm_engine* h, int* variant, int* drive_mode, int* num_obs);
+// drive mode and the observation width; for a PD plan also (each may be null) the first env of the second block (N with one block) and per
+// block the action scales of the step: act_scale (variant 0) and act_scale_se (variants 1 / 2)
+void lm_internal_replay_info(const lm_engine* h, int* variant, int* drive_mode, int* num_obs, int* split, float* act_scale, float* act_scale_se);
 // what a captured lm_step launch has baked into its kernel arguments and the engine may change afterwards: the goal / domain-randomisation seed
 // (lm_set_seed), which of the unclipped views are kept current (lm_ptr), and which kernels lm_step launches (lm_enable_contact_forces,
 // lm_enable_env_params).  A hipGraph captured under another key is re-captured.

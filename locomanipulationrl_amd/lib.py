@@ -30,6 +30,9 @@ REPLAY_ROWS = 32         # LM_REPLAY_ROWS (include/lm_policy.h)
 # rows of the replay record (qprev: the first of 12)
 REPLAY = dict(rows=0, finished=1, done_at=2, goal=3, row0_err=4, qerr=5, sq_sum=6, tracked=7, early=8, first_succ=9, in_window=10, min_v2=11, ret=12,
               window_return=13, v2_first=14, abs_sum=15, qprev=16)
+REPLAY_SATURATED, REPLAY_CMD_ERR = 28, 29      # written by PD plans in targets mode only
+REPLAY_CMD_ACTIONS, REPLAY_CMD_TARGETS = 0, 1  # LM_REPLAY_CMD_*
+ROW_SE = 90              # R_SE: the swing / extension position targets of variants 1 / 2 (12 rows)
 PTR_STATE, PTR_CNT, PTR_OBS_BUF, PTR_STATES_BUF, PTR_REW_BUF, PTR_EXTRAS, PTR_STATS, PTR_TERMS, PTR_DR_CNT, PTR_DR_PHYS, PTR_DR_RESET_STATE, PTR_DR_MASS, PTR_CONTACT, PTR_DR_ACTUATOR = range(14)
 PTR_ENV_PARAMS = 14      # LM_PTR_ENV_PARAMS
 ENV_PARAM_ROWS = DR_PHYS_ROWS + DR_MASS_ROWS + DR_ACTUATOR_ROWS      # LM_ENV_PARAM_ROWS = 69: the three records one after the other
@@ -74,7 +77,7 @@ EXPORTS = ["lm_create", "lm_destroy", "lm_set_reset_randomization", "lm_set_mass
            "lm_sample_actions", "lm_rollout_create", "lm_rollout_run", "lm_rollout_destroy",
            "lm_rollout_set_deterministic", "lm_rollout_set_episode_record", "lm_episode_update",
            "lm_rollout_set_trajectory_record", "lm_trajectory_update",
-           "lm_replay_create", "lm_replay_steps", "lm_replay_update", "lm_replay_destroy",
+           "lm_replay_create", "lm_replay_create_pd", "lm_replay_steps", "lm_replay_update", "lm_replay_destroy",
            "lm_mlp_grad_param_count", "lm_mlp_ppo_grad", "lm_mlp_ppo_grad_workspace", "lm_mlp_ppo_grad_geometry", "lm_gae",
            "lm_gnn_grad_param_count", "lm_gnn_ppo_grad", "lm_gnn_ppo_grad_workspace", "lm_gnn_ppo_grad_geometry",
            "lm_optim_state_len", "lm_optim_state_init", "lm_adam_clip_step", "lm_kl_adaptive_lr",
@@ -318,6 +321,7 @@ def load_library() -> C.CDLL:
     lib.lm_rollout_set_trajectory_record.argtypes = [vp, vp, ip, fp, vp, ip, ip]
     lib.lm_trajectory_update.argtypes = [vp, vp, ip, fp, vp, fp, vp, ip, ip, vp]
     lib.lm_replay_create.argtypes = [C.POINTER(vp), vp, fp, fp, vp, ip, ip, vp, ip, ip, ip, C.c_float, C.c_float, C.c_float]
+    lib.lm_replay_create_pd.argtypes = [C.POINTER(vp), vp, fp, fp, vp, ip, ip, vp, ip, ip, ip, C.c_float, C.c_float]
     lib.lm_replay_steps.argtypes = [vp]
     lib.lm_replay_update.argtypes = [vp, ip, fp, fp, fp, fp, vp]
     lib.lm_replay_destroy.argtypes = [vp]
@@ -1035,13 +1039,13 @@ class ReplayRecord:
         self.record[REPLAY["done_at"]] = -1.0; self.record[REPLAY["first_succ"]] = -1.0; self.record[REPLAY["min_v2"]] = float("inf")
 
     def update(self, plan, s: int, obs, rew, actions_next):
-        """After engine step number s (0: the reset step): obs (N, 64) and rew (N,) as that step wrote them; actions_next (N, 12) receives the
-        actions of step s + 1 (it may be the tensor step s read)."""
+        """After engine step number s (0: the reset step): obs (N, 64) - on a PD plan (N, engine.num_obs) - and rew (N,) as that step wrote
+        them; actions_next (N, 12) receives the actions of step s + 1 (it may be the tensor step s read)."""
         e, torch = self.engine, self.torch
         assert plan.engine is e, "the plan drives another engine"
         self.full = plan.full
         if self._native:
-            e._f32(obs, (self.N, NUM_OBS)); e._f32(rew, (self.N,)); e._f32(actions_next, (self.N, NUM_ACTIONS))
+            e._f32(obs, (self.N, e.num_obs if plan.pd else NUM_OBS)); e._f32(rew, (self.N,)); e._f32(actions_next, (self.N, NUM_ACTIONS))
             with torch.cuda.device(e.device):
                 e._check(e.lib.lm_replay_update(plan._h, int(s), Engine._p(obs), Engine._p(rew), Engine._p(self.record), Engine._p(actions_next), e._stream()))
             return
@@ -1073,14 +1077,35 @@ class ReplayRecord:
         cnt = e.cnt.to(dev); fin = live & (cnt[3] != 0)
         put(1, fin, torch.ones_like(v2)); put(2, fin, torch.full_like(v2, float(s))); put(3, fin, (cnt[2] != 0).to(torch.float32))
         go = live & ~fin & (s + 1 < T)
-        nxt = ((row(s + 1) - q) * plan.inv_full).clamp(-1.0, 1.0) if plan.servo else plan.act_t.to(dev)[rr, min(s + 1, plan.T_max - 1)].T
+        if plan.pd:
+            cmd = plan.act_t.to(dev); crow = lambda k: cmd[rr, min(max(k, 0), plan.T_max - 1)].T          # (12, N); only read where row k exists
+            if plan.cmd_mode == REPLAY_CMD_TARGETS:
+                def se_command(t):          # joint targets -> the swing / extension command of variants 1 / 2 (the inverse of the step's targets)
+                    c = t.clone()
+                    for l in range(4):
+                        c[4 + 2 * l] = 0.5 * (t[4 + 2 * l] + t[5 + 2 * l]); c[5 + 2 * l] = t[4 + 2 * l] - t[5 + 2 * l]
+                    return c
+                secmd = plan.variant_t.to(dev) >= 1
+                se = torch.where(secmd[None], f32(e.state[ROW_SE:ROW_SE + 12]), torch.zeros_like(q))
+                if s >= 1:
+                    put(REPLAY_CMD_ERR, inrec & secmd, torch.maximum(R[REPLAY_CMD_ERR], (se_command(crow(s)) - se).abs().max(0).values))
+                t = crow(s + 1)
+                raw = (torch.where(secmd[None], se_command(t), t) - se) * plan.inv_scale_t.to(dev)[None]
+                put(REPLAY_SATURATED, go, R[REPLAY_SATURATED] + (raw.abs() > 1.0).sum(0).to(torch.float32))
+                nxt = raw.clamp(-1.0, 1.0)
+            else:
+                nxt = crow(s + 1)
+        else:
+            nxt = ((row(s + 1) - q) * plan.inv_full).clamp(-1.0, 1.0) if plan.servo else plan.act_t.to(dev)[rr, min(s + 1, plan.T_max - 1)].T
         actions_next.copy_(torch.where(go[None], nxt, torch.zeros_like(nxt)).T.to(actions_next.device))
 
     def summary(self):
         """Host reduction per env, the quantities of the project's host replay (numpy arrays of shape (N,); envs that took no part have rows 0):
         rows, done_at and first_succ (-1: never), goal, row0_err, qerr, rms and mean_abs (joint error over the recorded rows), tracked (share
         of joint-steps within track_tol), early (mean joint-step error of the first four steps in units of a saturated action; needs the
-        plan's `full`), in_window, min_rd and rd_first = 2 asin(sqrt(v2)), return and window_return."""
+        plan's `full`; nan on a PD plan), in_window, min_rd and rd_first = 2 asin(sqrt(v2)), return and window_return; saturated (joint-steps
+        whose action left [-1, 1] before the clamp) and cmd_err (largest distance of the engine's held command from the logged one, rad):
+        both zero unless a PD plan ran in targets mode."""
         rec = self.record.detach().cpu().double().numpy()
         rows = rec[0]; steps = np.maximum(rows - 1.0, 0.0)
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -1088,7 +1113,8 @@ class ReplayRecord:
             return dict(rows=rows.astype(np.int64), finished=rec[1] != 0, done_at=rec[2].astype(np.int64), goal=rec[3].astype(np.int64), row0_err=rec[4], qerr=rec[5],
                         rms=np.sqrt(rec[6] / (12.0 * rows)), mean_abs=rec[15] / (12.0 * rows), tracked=rec[7] / (12.0 * steps),
                         early=rec[8] / (12.0 * np.minimum(4.0, steps) * (self.full if self.full else np.nan)), first_succ=rec[9].astype(np.int64),
-                        in_window=rec[10].astype(np.int64), min_rd=rd(rec[11]), rd_first=rd(rec[14]), window_return=rec[13], **{"return": rec[12]})
+                        in_window=rec[10].astype(np.int64), min_rd=rd(rec[11]), rd_first=rd(rec[14]), window_return=rec[13],
+                        saturated=rec[REPLAY_SATURATED].astype(np.int64), cmd_err=rec[REPLAY_CMD_ERR], **{"return": rec[12]})
 
 
 class ReplayPlan:
@@ -1099,16 +1125,29 @@ class ReplayPlan:
     full = act_scale x control period of the engine's blocks, computed in float64 and cast to float32.  servo=True steers every joint back onto
     the recording each step instead; `hold` zero-action rows follow a recording so that a late success streak can complete; `window_rows` and
     `succ_thresh` are the task's success window (rows and rot_dist in radians), `track_tol` the joint-step error that counts as tracked.
-    Velocity-drive engines with 64-wide observations only (the library refuses the others).  On an engine without the C library (the oracle
-    backend of the tests) the plan keeps its tables as torch tensors and ReplayRecord.update applies the rule in torch."""
+    PD-actuator engines (every block variant 1, variant 2, or variant 0 in position drive; lm_replay_create_pd) replay a command log and need
+    one of: `actions` (the logged action of every row; TrajectoryRecord's last_actions), `targets` (a list of (L, 12) arrays: the joint position
+    targets commanded for every row, in the recordings' joint order) or servo=True, which here means targets = the recordings themselves, so
+    that each step commands the recorded joints.  With none of the three a PD engine is refused as before; `targets` on a velocity-drive
+    engine is a ValueError.  A PD plan has no `full` (summary()'s `early` is nan).  On an engine without the C library (the oracle backend of
+    the tests) the plan keeps its tables as torch tensors and ReplayRecord.update applies the rule in torch."""
 
     def __init__(self, engine, recordings, env_rec, actions=None, servo: bool = False, hold: int = 2, window_rows: int = 17, succ_thresh: float = 0.15,
-                 track_tol: float = 1e-3):
+                 track_tol: float = 1e-3, targets=None):
         import torch
         self.torch, self.engine, self.N = torch, engine, int(engine.num_envs)
         recs = [np.asarray(a, dtype=np.float64) for a in recordings]
         if not recs or any(a.ndim != 2 or a.shape[1] != NUM_ACTIONS or a.shape[0] < 1 for a in recs):
             raise ValueError("recordings: a non-empty list of (L, 12) arrays is needed")
+        is_pd = lambda p: int(p.variant) in (1, 2) or (int(p.variant) == 0 and int(p.drive_mode) == 1)
+        pd_engine = all(is_pd(p) for p in engine.params)
+        if targets is not None and not pd_engine:
+            raise ValueError("targets: joint position targets drive PD-actuator blocks only (variant 1, variant 2, or variant 0 in position drive); "
+                             "this engine has a block in velocity or effort drive")
+        self.pd = pd_engine and (actions is not None or targets is not None or bool(servo))
+        if self.pd:
+            self._init_pd(recs, env_rec, actions, targets, servo, hold, window_rows, succ_thresh, track_tol)
+            return
         fulls = {float(p.act_scale) * float(p.ctrl_dt) for p in engine.params}
         if len(fulls) != 1:
             raise ValueError(f"the engine's blocks differ in act_scale x control period ({sorted(fulls)}): one plan scales every action alike")
@@ -1149,6 +1188,55 @@ class ReplayPlan:
                 raise ValueError("hold must be in [0, 8], every recording at least window_rows long and every id in [-1, R)")
             self.steps = int(max((int(lens[r]) + self.hold for r in set(ids[ids >= 0].tolist())), default=0))
 
+    def _init_pd(self, recs, env_rec, actions, targets, servo, hold, window_rows, succ_thresh, track_tol):
+        """A PD plan: the command table (actions or targets) instead of the action table, the scales read from the engine's blocks."""
+        torch, engine = self.torch, self.engine
+        if (actions is not None) + (targets is not None) + bool(servo) != 1:
+            raise ValueError("a PD engine replays ONE command log: give actions=, targets= or servo=True (targets = the recordings), not several")
+        self.cmd_mode = REPLAY_CMD_ACTIONS if actions is not None else REPLAY_CMD_TARGETS
+        name = "actions" if actions is not None else "targets"
+        cmds = recs if servo else [np.asarray(a, dtype=np.float64) for a in (actions if actions is not None else targets)]
+        if len(cmds) != len(recs) or any(a.shape != b.shape for a, b in zip(cmds, recs)):
+            raise ValueError(f"{name}: one (L, 12) array per recording is needed, of the recording's shape")
+        ids = np.asarray(env_rec.detach().cpu().numpy() if hasattr(env_rec, "detach") else env_rec)
+        if ids.shape != (self.N,) or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError(f"env_rec: an integer array of shape ({self.N},) is needed, got {ids.dtype} {ids.shape}")
+        self.R, self.T_max = len(recs), max(a.shape[0] for a in recs)
+        rec = np.zeros((self.R, self.T_max, NUM_ACTIONS), dtype=np.float32); cmd = np.zeros_like(rec)
+        for k, (a, b) in enumerate(zip(recs, cmds)):
+            rec[k, :a.shape[0]] = a; cmd[k, :a.shape[0]] = b
+        lens = np.asarray([a.shape[0] for a in recs], dtype=np.int32); ids = np.ascontiguousarray(ids, dtype=np.int32)
+        self.servo, self.hold, self.window_rows = bool(servo), int(hold), int(window_rows)
+        self.full, self.inv_full = None, float("nan")
+        self.v2_thresh = float(np.float32(np.sin(0.5 * float(succ_thresh)) ** 2)); self.track_tol = float(np.float32(track_tol))
+        dev = engine.cnt.device
+        self.rec_t, self.act_t = torch.from_numpy(rec).to(dev), torch.from_numpy(cmd).to(dev)
+        self.len_t, self.env_rec_t = torch.from_numpy(lens).to(dev), torch.from_numpy(ids).to(dev)
+        self._native = hasattr(engine, "lib") and hasattr(engine, "_h")
+        self._h = C.c_void_p()
+        # the plan's per-env view of the blocks, as the library forms it: the variant and the reciprocal of the action scale, in float, once
+        params = list(engine.params)
+        split = (engine.split_env if self._native else int(engine.split)) if len(params) == 2 else None
+        block = [params[1 if (split and e >= split) else 0] for e in range(self.N)]
+        inv = np.asarray([np.float32(1.0) / np.float32(b.act_scale_se if int(b.variant) >= 1 else b.act_scale) for b in block], dtype=np.float32)
+        self.variant_t = torch.tensor([int(b.variant) for b in block], dtype=torch.int64, device=dev)
+        self.inv_scale_t = torch.from_numpy(inv).to(dev)
+        if self._native:
+            p = lambda a: a.ctypes.data_as(C.c_void_p)
+            with torch.cuda.device(engine.device):
+                engine._check(engine.lib.lm_replay_create_pd(C.byref(self._h), engine._h, p(rec), p(cmd), p(lens), self.R, self.T_max, p(ids), self.cmd_mode, self.hold,
+                                                             self.window_rows, self.v2_thresh, self.track_tol))
+            self.steps = int(engine.lib.lm_replay_steps(self._h))
+            return
+        # the library's refusals, for a backend without it
+        if not np.isfinite(rec).all() or not np.isfinite(cmd).all():
+            raise ValueError("a table entry is not finite")
+        if not 0 <= self.hold <= 8 or self.window_rows < 1 or (lens < self.window_rows).any() or ids.min() < -1 or ids.max() >= self.R:
+            raise ValueError("hold must be in [0, 8], every recording at least window_rows long and every id in [-1, R)")
+        self.steps = int(max((int(lens[r]) + self.hold for r in set(ids[ids >= 0].tolist())), default=0))
+        if not np.isfinite(inv).all():
+            raise ValueError("a block whose action scale has no finite reciprocal")
+
     def run(self, record: ReplayRecord, zero: bool = True):
         """Replay on an engine whose envs are all about to reset (a fresh engine, or after reset_all()): for s = 0 .. steps - 1, Engine.step(actions)
         and then the record update, which also writes the next actions; nothing waits for the host inside the loop.  Returns the record."""
@@ -1157,7 +1245,7 @@ class ReplayPlan:
         if zero:
             record.zero()
         actions = torch.zeros((self.N, NUM_ACTIONS), dtype=torch.float32, device=dev)
-        obs = torch.empty((self.N, NUM_OBS), dtype=torch.float32, device=dev); rew = torch.empty((self.N,), dtype=torch.float32, device=dev)
+        obs = torch.empty((self.N, int(e.num_obs) if self.pd else NUM_OBS), dtype=torch.float32, device=dev); rew = torch.empty((self.N,), dtype=torch.float32, device=dev)
         for s in range(self.steps):
             e.step(actions, out_obs=obs, out_rew=rew)
             record.update(self, s, obs, rew, actions)

@@ -1,7 +1,9 @@
 """Replay of recorded joint motions over a grid of held per-env physics parameters: every (recording, grid point) pair is one env of ONE
 engine, driven along the recording by a lib.ReplayPlan and scored on the device (include/lm_policy.h, "replay of recorded joint motions").
 What a parameter fit needs - the 0.8 x friction fit of DESIGN.md 2.1 ran one value per process on the CPU oracle - and, with joint logs of
-a real robot in the recordings' format, a system-identification sweep over any of the 69 held rows.
+a real robot in the recordings' format, a system-identification sweep over any of the 69 held rows.  On the PD-actuator tasks (custom controller, position control, position
+drive) the recordings come with a command log - per recording the logged actions or the logged joint position targets - and the grid names
+kp_scale, kd_scale and latency fit the actuator from it.
 
 Layout: the locomotion recordings go on the block with the free base, the manipulation recordings on the block with the plate; inside a
 block env = first + file x points + point, and each block is padded to a multiple of 16 with envs that take no part (-1).
@@ -101,15 +103,23 @@ def sweep_engine(robot_model, params, layout: Dict, points: Sequence[Dict[str, f
 
 def replay_sweep(robot_model, params, recordings: Dict[str, np.ndarray], kinds: Dict[str, str], points: Sequence[Dict[str, float]], servo: bool = False,
                  hold: int = 2, window_rows: int = WINDOW_ROWS, succ_thresh: float = 0.15, track_tol: float = 1e-3, score_files: Optional[Sequence[str]] = None,
-                 seed: int = 0, max_envs: Optional[int] = None, engine_cls=Engine) -> Dict:
+                 seed: int = 0, max_envs: Optional[int] = None, engine_cls=Engine, actions: Optional[Dict[str, np.ndarray]] = None,
+                 targets: Optional[Dict[str, np.ndarray]] = None) -> Dict:
     """Replay every recording at every grid point on one fresh engine and score it on the device.  `params`: the engine's parameter block(s)
     (one, or a locomotion and a manipulation block); `recordings` {name: (L, 12)}; `kinds` {name: "loco" | "mani"}; `points` a list of
     {sweep name: value} (train.evaluate.sweep_grid; the names of SWEEP_NAMES).  The engine is created with dr_enabled and no channel, env
     params are enabled and the grid is held through sweep_env_params - the held `mu` row is mu_env itself, so mu = 0.8 is the shipped
     point.  Returns {"points", "runs": {point index: {file: summary in the shape of as_replay_run}}, "in_window": {point index: [rows inside
     the recorded success window per file of `score_files`]}, "shared": {point index: their sum}, "leave_one_out": the picks over `score_files`,
-    "files", "score_files", "layout", "steps"}.  `score_files` defaults to every recording."""
+    "files", "score_files", "layout", "steps"}.  `score_files` defaults to every recording.
+    PD-actuator blocks (lib.ReplayPlan) take the command log of every recording: `actions` {name: (L, 12)} (the logged actions; a trajectory
+    record's last_actions) or `targets` {name: (L, 12)} (the logged joint position targets), or servo=True (the recordings are the targets);
+    every summary then also carries `saturated` and `cmd_err`."""
     names = list(recordings)
+    for what, table in (("actions", actions), ("targets", targets)):
+        if table is not None and sorted(table) != sorted(names):
+            raise ValueError(f"{what}: one (L, 12) array per recording is needed, under the recordings' names (missing {sorted(set(names) - set(table))}, "
+                             f"unknown {sorted(set(table) - set(names))})")
     points = [dict(p) for p in points]
     lay = replay_layout(names, kinds, [p.mode for p in params], len(points), max_envs)
     score_files = list(names if score_files is None else score_files)
@@ -119,14 +129,18 @@ def replay_sweep(robot_model, params, recordings: Dict[str, np.ndarray], kinds: 
     eng = sweep_engine(robot_model, params, lay, points, seed=seed, engine_cls=engine_cls)
     try:
         plan = ReplayPlan(eng, [recordings[n] for n in names], lay["env_rec"], servo=servo, hold=hold, window_rows=window_rows, succ_thresh=succ_thresh,
-                          track_tol=track_tol)
+                          track_tol=track_tol, actions=None if actions is None else [actions[n] for n in names],
+                          targets=None if targets is None else [targets[n] for n in names])
         record = plan.run(ReplayRecord(eng))
         summ = record.summary()
         steps = plan.steps
         plan.close()
     finally:
         eng.close()
-    runs = {p: {n: as_replay_run({k: v[lay["env_of"][(n, p)]] for k, v in summ.items()}, len(recordings[n]), window_rows) for n in names} for p in range(len(points))}
+    def one(n, p):
+        e = lay["env_of"][(n, p)]
+        return dict(as_replay_run({k: v[e] for k, v in summ.items()}, len(recordings[n]), window_rows), saturated=int(summ["saturated"][e]), cmd_err=float(summ["cmd_err"][e]))
+    runs = {p: {n: one(n, p) for n in names} for p in range(len(points))}
     table = {p: [runs[p][n]["in_window"] for n in score_files] for p in range(len(points))}
     return dict(points=points, runs=runs, in_window=table, shared={p: int(sum(v)) for p, v in table.items()}, leave_one_out=leave_one_out(table, score_files),
                 files=names, score_files=score_files, layout=lay, steps=steps)

@@ -3,11 +3,16 @@
 pair on the device (train/replay.py, include/lm_policy.h "replay of recorded joint motions"): a parameter fit, or system identification
 from joint logs, in one run.
     python tools/replay_sweep.py --recordings tests/golden/npy_traj.npz [--npy FILE:loco|mani ...] --sweep mu=0.5:1.2:8 [--sweep ...] [--servo] [--out JSON]
+    python tools/replay_sweep.py --task QuadrupedPoseControlCustomController --log robot_log.npz --sweep kp_scale=0.5:2:16 --sweep latency=0:4:5
 --recordings takes an .npz of (L, 12) arrays (the reference's RECORD_JOINT files: byte-identical duplicates are replayed once; an array is a
 manipulation recording when the part of its name in front of "from" contains "mani"), --npy single files as TrajectoryRecord.save_npy and the
 reference write them.  --sweep NAME=LO:HI:K as tools/eval_policy.py (several form their Cartesian product; mu is the contact coefficient
-itself: 0.8 is the shipped value).  The blocks are those of the co-training task the reference recorded (JointLocomanipulation) with the goal
-fixed at --goal (default: the goal the committed reference code recorded under; "task" keeps the task's range).  --score names the
+itself: 0.8 is the shipped value).  The blocks are those of --task (any shipped task YAML; default: the co-training task the reference recorded,
+JointLocomanipulation) with the goal fixed at --goal (default on the default task: the goal the committed reference code recorded under; "task",
+the default on any other task, keeps the task's range).  --log takes an .npz of a command-and-joint log for the PD-actuator tasks (custom
+controller, position control): per recording NAME the keys q_NAME (L, 12) - the measured joints - and ONE of actions_NAME (L, 12) - the action
+of every control step, row 0 the reset step's - or targets_NAME (L, 12) - the joint position targets commanded for every step, in the joints'
+order; every recording of a file carries the same of the two.  --score names the
 recordings the window table and the leave-one-out picks are taken over; --repeat runs the sweep several times in one process (timing).
 Prints one JSON line: per grid point its values, the rows inside the recorded success window per file and their sum, per file the replay's
 summary; the leave-one-out picks; the wall time of the sweep (engine creation to summary) in seconds."""
@@ -38,13 +43,25 @@ def load_recordings(npz, npy):
             raise SystemExit(f"--npy {spec!r}: FILE:loco or FILE:mani is needed")
         name = os.path.splitext(os.path.basename(path))[0]
         recs[name] = np.load(path).astype(np.float64); kinds[name] = kind
-    if not recs:
-        raise SystemExit("no recording: give --recordings and / or --npy")
     return recs, kinds
 
 
+def load_log(path, recs, kinds):
+    """The recordings of a command-and-joint log added to recs / kinds; returns ("actions" | "targets", {name: (L, 12)})."""
+    g = np.load(path)
+    names = [k[2:] for k in g.files if k.startswith("q_")]
+    if not names:
+        raise SystemExit(f"--log {path}: no q_NAME array")
+    which = [w for w in ("actions", "targets") if all(f"{w}_{n}" in g.files for n in names)]
+    if len(which) != 1:
+        raise SystemExit(f"--log {path}: every recording needs actions_NAME, or every recording targets_NAME (and not both)")
+    for n in names:
+        recs[n] = g["q_" + n].astype(np.float64); kinds[n] = kind_of(n)
+    return which[0], {n: g[f"{which[0]}_{n}"].astype(np.float64) for n in names}
+
+
 def jsonable(r):
-    return {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in r.items()}
+    return {k: (v.tolist() if isinstance(v, np.ndarray) else None if isinstance(v, float) and v != v else v) for k, v in r.items()}          # (a PD plan has no `early`: nan)
 
 
 def main():
@@ -52,7 +69,9 @@ def main():
     ap.add_argument("--recordings", default=None, help=".npz of (L, 12) joint trajectories")
     ap.add_argument("--npy", action="append", default=[], metavar="FILE:loco|mani", help="one (L, 12) .npy and the block that replays it (repeatable)")
     ap.add_argument("--sweep", action="append", default=[], metavar="NAME=LO:HI:K", help="hold a grid of per-env parameters (repeatable: Cartesian product)")
-    ap.add_argument("--goal", default="0.2,0.2,0.785", help="roll,pitch,yaw the recordings were made under, or 'task'")
+    ap.add_argument("--task", default=TASK, help="the task YAML whose parameter blocks replay the recordings")
+    ap.add_argument("--log", default=None, help=".npz command-and-joint log of a PD-actuator task: q_NAME and actions_NAME or targets_NAME per recording")
+    ap.add_argument("--goal", default=None, help="roll,pitch,yaw the recordings were made under, or 'task' (default: 0.2,0.2,0.785 on the default task, 'task' otherwise)")
     ap.add_argument("--servo", action="store_true", help="steer the joints back onto the recording every step instead of replaying the recovered actions")
     ap.add_argument("--repeat", type=int, default=1, help="run the sweep this many times (wall times are listed)")
     ap.add_argument("--score", default=None, help="comma-separated recordings the window table and the leave-one-out picks are taken over (default: all)")
@@ -69,10 +88,21 @@ def main():
     except ValueError as e:
         raise SystemExit(str(e))
     recs, kinds = load_recordings(a.recordings, a.npy)
-    task = task_map()[TASK](name=TASK, sim_config=SimConfig(load_config(TASK, num_envs=32)), env=None)
+    command = {}
+    if a.log:
+        if recs:
+            raise SystemExit("--log carries its own recordings: it does not combine with --recordings / --npy")
+        which, table = load_log(a.log, recs, kinds)
+        command = {which: table}
+    if not recs:
+        raise SystemExit("no recording: give --recordings, --npy or --log")
+    if a.task not in task_map():
+        raise SystemExit(f"--task {a.task!r}: one of {sorted(task_map())}")
+    task = task_map()[a.task](name=a.task, sim_config=SimConfig(load_config(a.task, num_envs=32)), env=None)
     params = task.engine_params()
-    if a.goal != "task":
-        goal = [float(x) for x in a.goal.split(",")]
+    goal_arg = a.goal if a.goal is not None else ("0.2,0.2,0.785" if a.task == TASK else "task")
+    if goal_arg != "task":
+        goal = [float(x) for x in goal_arg.split(",")]
         params = [dataclasses.replace(p, goal_lo=goal, goal_hi=goal) for p in params]
     build_library()
     rm = load_model(task.model_asset)
@@ -81,11 +111,11 @@ def main():
     try:
         for _ in range(max(a.repeat, 1)):
             t0 = time.perf_counter()
-            out = replay_sweep(rm, params, recs, kinds, points, servo=a.servo, score_files=score)
+            out = replay_sweep(rm, params, recs, kinds, points, servo=a.servo, score_files=score, **command)
             walls.append(time.perf_counter() - t0)
     except ValueError as e:
         raise SystemExit(str(e))
-    line = json.dumps({"task": TASK, "servo": bool(a.servo), "num_envs": out["layout"]["num_envs"], "steps": out["steps"], "files": out["files"],
+    line = json.dumps({"task": a.task, "servo": bool(a.servo), "num_envs": out["layout"]["num_envs"], "steps": out["steps"], "files": out["files"],
                        "score_files": out["score_files"],
                        "points": [{"point": out["points"][p], "in_window": out["in_window"][p], "shared": out["shared"][p],
                                    "runs": {n: jsonable(r) for n, r in out["runs"][p].items()}} for p in range(len(out["points"]))],
